@@ -8,7 +8,7 @@ y0 = [0, 1].  A "step" = one solve of the whole batch (one kernel launch) + the 
 epilogue + the loss reduction; with N > 1 GPUs every rank solves its own B trajectories (weak scaling,
 no data-path collective) and the scalar loss is all-reduced over RCCL.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--nt NT] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--nt NT] [--no-cpu-baseline] [--dump-outputs DIR]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline`.
@@ -36,6 +36,8 @@ P_HH = np.array([1.12592345582957387e-01, 8.26751134920666146e+01, 3.38768033864
 MLP_L, MLP_N = 5, 200  # architectures/s00.py
 F_MLP = 2 * (MLP_L * MLP_N * MLP_N + 3 * MLP_N)  # 401 200 FLOP per RHS evaluation
 F_RHS_OTHER = 150  # HH rate terms + RK stage combination per evaluation
+DUMP_BYTES = 64 * 10**6  # --dump-outputs: size limit of everything written
+DUMP_SEED = 20240601  # --dump-outputs: which trajectories (and output times) the sample keeps
 
 
 def load_weights():
@@ -68,8 +70,13 @@ def main():
                          "of the N > 1 path with one rank on a 1-GPU box")
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="rehearsal of the N > 1 code path on a 1-GPU box: every rank uses cuda:0 (use with gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (a fixed sample of y and i, "
+                         f"at most {DUMP_BYTES // 10**6} MB in all)")
     ap.add_argument("--python-prefix-worker", nargs=3, type=int, metavar=("I", "N", "NT"), help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.python_prefix_worker:   # a child of the cpu_baseline_python leg: CPU only, never initialises the GPU
         return _python_prefix_worker(*args.python_prefix_worker)
@@ -194,6 +201,9 @@ def main():
         per_rank = {"per_rank_ms": [float(b[0]) for b in both], "per_rank_kernel_ms": [float(b[1]) for b in both],
                     "allreduce_16B_us": (time.perf_counter() - ta) / 20 * 1e6}
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r, loss, first, rank, world)
+
     stats = r["stats"].cpu().numpy()
     status = r["status"].cpu().numpy()
     nfe = stats[:, 2].astype(np.float64)
@@ -298,6 +308,33 @@ def main():
         print(json.dumps(res))
     if dist is not None:
         dist.destroy_process_group()
+
+
+def dump_outputs(d, r, loss, first, rank, world):
+    """What the last timed step returned, as float64 .npy files: loss, every trajectory's status and stats, and y / i of a fixed,
+    seeded sample of whole trajectories (indices in traj_index.npy, global over the ranks) that keeps the dump within DUMP_BYTES.
+    Rank 0 writes to d, rank k > 0 to d/rank<k>; the budget is shared by the ranks."""
+    if rank > 0:
+        d = os.path.join(d, f"rank{rank}")
+    os.makedirs(d, exist_ok=True)
+    y, i = r["y"], r["i"]
+    B, Nt = i.shape
+    per_sample = (y.shape[2] + 1) * 8                      # y[:, k, :] and i[:, k], both written as float64
+    room = DUMP_BYTES // world - B * (1 + 4 + 1) * 8 - 64 * 1024  # status, stats, traj_index, loss and the .npy headers
+    if room < per_sample + 8:
+        raise SystemExit(f"--dump-outputs: {B} trajectories' status and stats alone exceed {DUMP_BYTES} bytes")
+    cols = torch.arange(Nt, device=i.device)
+    if Nt * (per_sample + 8) > room:                       # not even one whole trajectory fits: a seeded sample of output times
+        n = room // (per_sample + 8)
+        cols = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED + 1).choice(Nt, n, replace=False))).to(i.device)
+    k = min(B, (room - len(cols) * 8) // (len(cols) * per_sample))  # t_index takes 8 bytes per output time
+    rows = np.arange(B) if k == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, k, replace=False))
+    sel = torch.from_numpy(rows).to(i.device)
+    arrays = {"y": y.index_select(0, sel).index_select(1, cols), "i": i.index_select(0, sel).index_select(1, cols),
+              "status": r["status"], "stats": r["stats"], "loss": loss.reshape(1),
+              "traj_index": torch.from_numpy(rows + first), "t_index": cols}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), a.detach().cpu().numpy().astype(np.float64))
 
 
 def pmc_summary(lib_sha):

@@ -119,14 +119,16 @@ def test_checkpoint_round_trip_and_reference_files(tmp_path):
     func = M.NNf(K.P_HH)
     func.load_state_dict(torch.load(path, weights_only=True)["state_dict"])
     assert np.array_equal(func.net[0].weight.detach().numpy().ravel(), w[:400])
-    ref = "/root/reference"
-    if os.path.exists(os.path.join(ref, "s1", "model-state-dict.pt")):  # build container only: the reference's own files
-        assert np.array_equal(pp.load_checkpoint(os.path.join(ref, "s1", "model-state-dict.pt"))["flat"], w)
-        best = os.path.join(ref, "r1", "best-model-checkpoint.pt")
-        if os.path.exists(best):
-            ck = pp.load_checkpoint(best)
-            assert ck["epoch"] == 401 and (ck["mlp_layers"], ck["mlp_width"]) == (5, 200) and ck["flat"].size == 201801
-            assert abs(float(ck["loss"][0]) - 0.1058) < 1e-3 and "param_groups" in ck["optimizer"]
+    # the reference's own r1/best-model-checkpoint.pt (tests/golden/make_checkpoint_fixture.py: Adam moments dropped)
+    best = os.path.join(os.path.dirname(__file__), "golden", "checkpoint_r1_best.pt")
+    ck = pp.load_checkpoint(best)
+    assert ck["epoch"] == 401 and (ck["mlp_layers"], ck["mlp_width"]) == (5, 200) and ck["flat"].size == 201801
+    assert abs(float(ck["loss"][0]) - 0.1058) < 1e-3 and "param_groups" in ck["optimizer"]
+    # a bare state dict, as the reference writes model-state-dict.pt (torch.save(model.state_dict())), of the reference's tensors
+    bare = str(tmp_path / "model-state-dict.pt")
+    torch.save(torch.load(best, weights_only=True)["state_dict"], bare)
+    bk = pp.load_checkpoint(bare)
+    assert np.array_equal(bk["flat"], ck["flat"]) and (bk["mlp_layers"], bk["mlp_width"]) == (5, 200) and bk["epoch"] is None
 
 
 def test_multi_exp_is_the_references_tri_and_bi_exponential(pre):
