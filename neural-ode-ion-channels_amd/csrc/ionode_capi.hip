@@ -1,7 +1,9 @@
 // ionode_capi.hip -- the C ABI of libionode.so (include/ionode.h): argument checking, choice of
 // kernel instantiation and launch geometry, and the host-side re-layout of an nn.Sequential
 // state dict into the MFMA fragment order the kernels stream.
+#include <algorithm>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <vector>
 
@@ -38,6 +40,7 @@ struct Plan {
   unsigned block = 0;
   size_t lds = 0;
   size_t lw_bytes = 0;   // lane-wise kernels: LDS bytes of one wavefront's region (the workgroup reserves four)
+  bool tile_shrink = false;   // lean N = 200 16-tile: the tail of a tile runs on the 4-trajectory net (KArgs::tile_shrink)
 };
 
 
@@ -193,6 +196,13 @@ int make_plan(const ionode_desc *d, Plan *pl, bool want_current = false, bool ex
     else if (t1) pl->lds = t1deep ? ionode::MlpRow1Deep::lds_bytes(d->mlp_layers) : ionode::MlpRow1::lds_bytes(d->mlp_layers);
     else if (t4) pl->lds = ionode::MlpTile4::lds_bytes(d->mlp_layers);
     else if (Gv == 4 && NT == 13) pl->lds = t32 ? ionode::MlpTile<4, 4, 13, 13, 4>::lds_total(d->mlp_layers) : ionode::MlpTile<4, 4, 13, 13, 0>::lds_total(d->mlp_layers);
+    // the lean 16-tile hands its LDS region to the 4-trajectory net when <= 4 of a tile's trajectories are left (MlpShrink4).  On by
+    // default; IONODE_TILE_SHRINK=0 turns it off (dev override for A/B runs, read per plan)
+    if (Gv == 4 && NT == 13 && !t32 && !t4 && !t1 && leanm) {
+      const char *ts = getenv("IONODE_TILE_SHRINK");
+      pl->tile_shrink = ts == nullptr || ts[0] == '\0' || atoi(ts) != 0;
+      pl->lds = std::max(pl->lds, ionode::MlpTile4::lds_bytes(d->mlp_layers));
+    }
     if (t64) plan_lane_wise(pl, (size_t)((d->n_traj + 63) / 64), (vnet ? (size_t)0 : ((pl->lds + 15) & ~(size_t)15)) + (size_t)ionode::LwLds::bytes(2, t64lean));  // MlpTile region + the lane-wise region
   }
   if (!pl->v) { set_err("no kernel variant compiled for this descriptor"); return IONODE_ERR_UNSUPPORTED; }
@@ -538,6 +548,7 @@ int ionode_dopri5(const ionode_desc *d, const float *mlp_packed, const double *p
   a.te_t0 = d->t_eval_t0_hint; a.te_dt = (d->t_eval_dt_hint > 0.0 && d->n_out > 1) ? d->t_eval_dt_hint : 0.0;
   a.te_rdt = a.te_dt > 0.0 ? 1.0 / a.te_dt : 0.0;
   a.te_exact = (a.te_dt > 0.0 && d->t_eval_exact) ? 1 : 0;
+  a.tile_shrink = pl.tile_shrink ? 1 : 0;
   const hipError_t e = pl.v->fn(a, pl.grid, pl.lds, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) { set_err("kernel launch failed: %s", hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
   g_last_kernel = pl.v->name;
