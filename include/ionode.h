@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define IONODE_ABI_VERSION 9
+#define IONODE_ABI_VERSION 10
 
 /* RHS families (func.forward variants of the reference) */
 #define IONODE_MODEL_HH2 0     /* 2-state Hodgkin-Huxley: Lambda, train-s1.py:134-177; candidate ODEFunc train-d0.py:321-374 */
@@ -224,6 +224,21 @@ int ionode_dopri5_backward(const ionode_desc *d, int32_t it_begin, int32_t it_en
                            const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                            const double *t_eval, const int32_t *n_accepted, const void *grad_y, double *state,
                            float *records, double *grad_params, double *grad_y0, void *stream);
+
+/*
+ * Fused sum-of-squares gradient (closed-form HH 2-state and 6-state models; since ABI 10): the same sweep as
+ * ionode_dopri5_backward, for the objective sse[b] = sum_k (i_k - sse_ref[protocol][k])^2 of the fused forward (i as in the
+ * i_out epilogue, sample 0 = y0 included).  The upstream gradient is one scalar per trajectory, grad_sse[b] = dL/dsse[b]; the
+ * sweep re-evaluates each output sample from the step's checkpoint and forms dL/dy_k itself, so neither y nor dL/dy is ever
+ * materialised.  The forward is ionode_dopri5 with d->ckpt and d->sse_out set (y_out = i_out = NULL allowed).  Reads sse_ref,
+ * obs_g, obs_e, obs_open_state_only, v_at_outputs (optional), ckpt and ckpt_cap from the descriptor; chunking over iterations,
+ * n_accepted, state, grad_params and grad_y0 as for ionode_dopri5_backward (n_accepted[b] = 0: zero rows).  IONODE_ERR_ARG when
+ * sse_ref, ckpt or grad_sse is NULL; IONODE_ERR_UNSUPPORTED for the NN models and for traj_per_image > 0.
+ */
+int ionode_dopri5_backward_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *params,
+                               const double *prot_v, const double *prot_t, const int32_t *prot_of_traj, const double *t_eval,
+                               const int32_t *n_accepted, const double *grad_sse, double *state, double *grad_params,
+                               double *grad_y0, void *stream);
 
 /*
  * Two-phase form of the same sweep (NN-f / NN-d).  A stage's vector-Jacobian product is LINEAR in its seed, and the seed is a scalar

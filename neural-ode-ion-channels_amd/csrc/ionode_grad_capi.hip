@@ -147,6 +147,41 @@ int ionode_dopri5_backward(const ionode_desc *d, int32_t it_begin, int32_t it_en
                        state, records, nullptr, grad_params, grad_y0, stream);
 }
 
+int ionode_dopri5_backward_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *params,
+                               const double *prot_v, const double *prot_t, const int32_t *prot_of_traj, const double *t_eval,
+                               const int32_t *n_accepted, const double *grad_sse, double *state, double *grad_params,
+                               double *grad_y0, void *stream) {
+  if (!d) { gerr("null descriptor"); return IONODE_ERR_ARG; }
+  if (d->model != IONODE_MODEL_HH2 && d->model != IONODE_MODEL_MARKOV6) {
+    gerr("ionode_dopri5_backward_sse: closed-form models only (HH 2-state, 6-state)"); return IONODE_ERR_UNSUPPORTED;
+  }
+  if (d->traj_per_image > 0) { gerr("ionode_dopri5_backward_sse: traj_per_image must be 0"); return IONODE_ERR_UNSUPPORTED; }
+  const bool m6 = d->model == IONODE_MODEL_MARKOV6;
+  if (d->n_state != (m6 ? 6 : 2) || d->n_traj < 1 || d->n_out < 1 || d->n_prot < 1 || d->prot_n < 2 || d->n_params < (m6 ? 12 : 8) || !(d->prot_dt > 0)) {
+    gerr("inconsistent descriptor"); return IONODE_ERR_ARG;
+  }
+  if (!d->sse_ref || !grad_sse || !d->ckpt || d->ckpt_cap < 1 || !params || !prot_v || !t_eval || !n_accepted || !state || !grad_params || !grad_y0) {
+    gerr("ionode_dopri5_backward_sse: required buffer is NULL (sse_ref / ckpt / ckpt_cap come from the descriptor)"); return IONODE_ERR_ARG;
+  }
+  if (it_begin < 0 || it_end <= it_begin || it_end > n_iter) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
+  ionode::GArgs a;
+  memset(&a, 0, sizeof a);
+  a.k.params = params; a.k.prot_v = prot_v; a.k.prot_t = prot_t; a.k.prot_of_traj = prot_of_traj; a.k.t_eval = t_eval;
+  a.k.B = d->n_traj; a.k.Nt = d->n_out; a.k.P = d->n_prot; a.k.Np = d->prot_n; a.k.n_params = d->n_params;
+  a.k.NP = 16; a.k.NT = 1;
+  a.k.prot_t0 = d->prot_t0; a.k.prot_dt = d->prot_dt; a.k.prot_rdt = 1.0 / d->prot_dt; a.k.v_oob = d->v_oob;
+  a.ckpt = d->ckpt; a.ckpt_cap = d->ckpt_cap; a.nacc = n_accepted; a.state = state; a.grad_params = grad_params; a.grad_y0 = grad_y0;
+  a.it_begin = it_begin; a.it_end = it_end; a.n_iter = n_iter;
+  a.grad_sse = grad_sse; a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
+  a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
+  SweepFn fn = m6 ? (d->state_f32 ? &ionode::launch_sweep_sse<IONODE_MODEL_MARKOV6, float> : &ionode::launch_sweep_sse<IONODE_MODEL_MARKOV6, double>)
+                  : (d->state_f32 ? &ionode::launch_sweep_sse<IONODE_MODEL_HH2, float> : &ionode::launch_sweep_sse<IONODE_MODEL_HH2, double>);
+  fn(a, (unsigned)((d->n_traj + 15) / 16), (size_t)16 * 5 * (m6 ? 6 : 2) * 8, reinterpret_cast<hipStream_t>(stream));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { gerr(hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
+  return IONODE_OK;
+}
+
 size_t ionode_grad_packet_doubles(void) { return (size_t)16 * ionode::GRAD_PACKET; }
 
 int ionode_dopri5_backward_recompute(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,

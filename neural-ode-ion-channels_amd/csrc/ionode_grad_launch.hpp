@@ -33,6 +33,13 @@ void launch_sweep(const GArgs &a, unsigned grid, size_t lds, hipStream_t s) {
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
 }
 
+// the fused sum-of-squares sweep of the closed-form models (ionode_dopri5_backward_sse)
+template <int MODEL, typename S>
+void launch_sweep_sse(const GArgs &a, unsigned grid, size_t lds, hipStream_t s) {
+  auto kern = ionode_dopri5_backward_sse_kernel<MODEL, S>;
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, a);
+}
+
 template <int NT> SweepFn pick_sweep(int model, int f32) {
   if (model == IONODE_MODEL_NNF) return f32 ? &launch_sweep<IONODE_MODEL_NNF, float, NT> : &launch_sweep<IONODE_MODEL_NNF, double, NT>;
   return f32 ? &launch_sweep<IONODE_MODEL_NND, float, NT> : &launch_sweep<IONODE_MODEL_NND, double, NT>;

@@ -363,3 +363,133 @@ def allreduce_gradients(tensors, group=None):
         out.append(flat[off:off + t.numel()].reshape(t.shape).to(t.dtype))
         off += t.numel()
     return out
+
+
+class _SumOfSquares(torch.autograd.Function):
+    """sse[B] = sum_k (i_k - sse_ref[protocol][k])^2 of the fused forward; differentiable in (params, y0).  Nothing of size
+    [B, Nt] is ever allocated: forward ionode_dopri5 with checkpoints and sse_out (no state trace), backward
+    ionode_dopri5_backward_sse with the [B] upstream gradient."""
+
+    @staticmethod
+    def forward(ctx, params, y0, cfg):
+        dev = y0.device
+        B, D = y0.shape
+        cap = int(cfg.get("ckpt_cap") or DEFAULT_CKPT_CAP)
+        # checkpoint sizing, regrowth and budget: the rules of _Solve.forward
+        limit = _bounded_budget(cfg.get("ckpt_budget_bytes"), DEFAULT_CKPT_BUDGET, dev, 0.6)
+        row_bytes = B * (4 + 8 * D) * 8
+        if cap * row_bytes > limit:
+            cap = max(1, limit // row_bytes)
+        while True:
+            ckpt = None   # (a regrown buffer replaces the old one instead of coexisting with it)
+            ckpt = torch.empty((B, cap, 4 + 8 * D), dtype=torch.float64, device=dev)
+            r = capi.dopri5(cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], prot_t=cfg["prot_t"],
+                            prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"], prot_of_traj=cfg["prot_of_traj"], rtol=cfg["rtol"],
+                            atol=cfg["atol"], v_oob=cfg["v_oob"], max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"],
+                            max_step=cfg["max_step"], ckpt=ckpt, obs_g=cfg["obs_g"], obs_e=cfg["obs_e"],
+                            obs_open_state_only=cfg["obs_open_state_only"], t_eval_hint=cfg["t_eval_hint"],
+                            sse_ref=cfg["sse_ref"], states=False)
+            nacc = torch.where(r["status"] == 0, r["stats"][:, 0], torch.zeros_like(r["stats"][:, 0]))
+            most = int(nacc.max().item())
+            if most <= cap:
+                break
+            cap = 1 << int(np.ceil(np.log2(most + 1)))
+            if cap * row_bytes > limit and most * row_bytes <= limit:
+                cap = limit // row_bytes
+            need = cap * row_bytes
+            if need > limit:
+                raise capi.IonodeError(f"checkpoints of {most} accepted steps x {B} trajectories need {need / 2**30:.1f} GiB "
+                                       f"(> ckpt_budget_bytes = {limit / 2**30:.1f} GiB): split the batch or raise the budget")
+        ctx.cfg, ctx.desc = cfg, r["desc"]
+        ctx.vtab = r["v_at_outputs"]   # the descriptor points at it: the backward reads V(t_k) from the same table
+        ctx.sdt = y0.dtype
+        ctx.save_for_backward(params.detach(), ckpt, r["stats"], r["status"])
+        ctx.mark_non_differentiable(r["status"])
+        return r["sse"], r["status"]
+
+    @staticmethod
+    def backward(ctx, g_sse, _gstatus):
+        cfg, desc = ctx.cfg, ctx.desc
+        params, ckpt, stats, status = ctx.saved_tensors
+        dev = params.device
+        B, D = desc.n_traj, desc.n_state
+        npar = 12 if desc.model == capi.MODEL_MARKOV6 else 8
+        failed = status != 0
+        # failed trajectories (sse = inf): their upstream rows are ignored and their gradient rows are zero
+        g = torch.where(failed, torch.zeros((), dtype=torch.float64, device=dev), g_sse.to(torch.float64)).contiguous()
+        n_acc = torch.where(failed, torch.zeros_like(stats[:, 0]), stats[:, 0]).to(torch.int32).contiguous()
+        n_iter = int(n_acc.max().item()) + 1
+        state = torch.empty((B, 2 * D + npar), dtype=torch.float64, device=dev)
+        g_params = torch.zeros((B, npar), dtype=torch.float64, device=dev)
+        g_y0 = torch.zeros((B, D), dtype=torch.float64, device=dev)
+        desc.ckpt, desc.ckpt_cap = ckpt.data_ptr(), ckpt.shape[1]
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        rc = capi.lib().ionode_dopri5_backward_sse(C.byref(desc), 0, n_iter, n_iter, _ptr(params), _ptr(cfg["prot_v"]),
+                                                   _ptr(cfg["prot_t"]), _ptr(cfg["prot_of_traj"]), _ptr(cfg["t_eval"]), _ptr(n_acc),
+                                                   _ptr(g), _ptr(state), _ptr(g_params), _ptr(g_y0), stream)
+        if rc != 0:
+            raise capi.IonodeError(f"ionode_dopri5_backward_sse failed ({rc}): {capi.lib().ionode_grad_last_error().decode()}")
+        g_params[failed] = 0.0
+        g_y0[failed] = 0.0
+        return (g_params if ctx.needs_input_grad[0] else None), (g_y0.to(ctx.sdt) if ctx.needs_input_grad[1] else None), None
+
+
+def uniform_grid_hint(t_eval):
+    """(t0, dt) of a uniform output grid -- what the fused objective's output cursor needs (ionode_desc.t_eval_dt_hint; the
+    kernel verifies it against t_eval) -- or None: capi.dopri5's "auto" rule (every t_k within dt / 2 of t0 + k dt)."""
+    n = int(t_eval.shape[0])
+    if n < 2:
+        return None
+    t0 = t_eval[0]
+    dt = (t_eval[n - 1] - t0) / (n - 1)
+    dev = (t_eval - (t0 + torch.arange(n, dtype=torch.float64, device=t_eval.device) * dt)).abs().max()
+    v = torch.stack([t0, dt, dev]).cpu()
+    return (float(v[0]), float(v[1])) if float(v[1]) > 0 and float(v[2]) <= 0.5 * float(v[1]) else None
+
+
+def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, prot_t0=0.0, prot_dt=1.0, prot_of_traj=None,
+                   obs_g=1.0, obs_e=-86.0, obs_open_state_only=False, rtol=1e-7, atol=1e-9, v_oob=-80.0, max_steps=0,
+                   max_total_steps=0, max_step=0.0, ckpt_cap=None, ckpt_budget_bytes=None):
+    """Fused sum-of-squares objective with its gradient (PINTS SumOfSquaresError.evaluateS1 over a batch; closed-form HH 2-state
+    and 6-state models).
+
+    sse[b] = sum_k (i_k - sse_ref[protocol(b)][k])^2, i_k = obs_g * gate(y_k) * (V(t_k) - obs_e), gate = y0 * y1 (or the last
+    state with obs_open_state_only), k = 0 .. Nt - 1 (sample 0 is y0): the objective of batched.solve(sse_ref=..., states=False).
+    params [B, 8 | 12] fp64, y0 [B, D] fp32 | fp64 (the state dtype), prot_v [P, Np], t_eval [Nt], sse_ref [P, Nt] fp64 -- device
+    tensors; params and y0 may require grad.  Returns (sse [B] fp64, status [B] int32), differentiable in params and y0: the exact
+    derivative of the discretisation the forward executed, as grad.solve's.  Failed trajectories (status != 0) give sse = inf;
+    their upstream values are ignored and their dL/dp, dL/dy0 rows are zero.
+
+    Neither the states nor the current trace nor dL/dy is ever materialised: the forward writes accepted-step checkpoints and
+    the per-trajectory sums only, and the backward sweep (ionode_dopri5_backward_sse) re-evaluates every output sample from the
+    checkpoints and forms dL/dy_k in the kernel.  Memory: the checkpoints (sized, regrown and bounded by ckpt_cap /
+    ckpt_budget_bytes as in grad.solve) plus O(B).  The output grid must be uniform (the fused forward's output cursor); for any
+    other t_eval use the materialised route, grad.solve followed by the sum of squares in torch.  max_step: as grad.solve."""
+    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
+        raise capi.IonodeError("grad.sum_of_squares: the fused objective gradient is built for the closed-form HH 2-state and 6-state "
+                               "models; for NN models use grad.solve and form the sum of squares in torch")
+    if isinstance(max_step, str):
+        if max_step != "auto":
+            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
+        max_step = stable_step_cap(model, params, prot_v, v_oob)
+    elif float(max_step) == 0.0 and isinstance(params, torch.Tensor) and params.requires_grad:
+        import warnings
+        warnings.warn("gradients w.r.t. the rate parameters through an UNCAPPED dopri5 solve: at equilibria dopri5 accepts steps with "
+                      "h*lambda >> 1 whose exact derivative amplifies rounding noise without bound (|dL/dp| ~ 1e36 on long holds, "
+                      "DESIGN.md 5.4).  Pass max_step='auto' (= 3 / lambda_max of the rate constants, grad.stable_step_cap) or a "
+                      "value in ms; the forward values then follow the capped step sequence.", RuntimeWarning, stacklevel=2)
+    if not (isinstance(y0, torch.Tensor) and y0.is_cuda):
+        raise capi.IonodeError("no HIP tensors: the integrator and its backward sweep have no CPU path")
+    D = 6 if model == capi.MODEL_MARKOV6 else 2
+    if y0.dim() != 2 or y0.shape[1] != D or params.dim() != 2 or params.shape[0] != y0.shape[0]:
+        raise capi.IonodeError(f"params [B, {12 if D == 6 else 8}] and y0 [B, {D}] expected")
+    hint = uniform_grid_hint(t_eval)
+    if hint is None:
+        raise capi.IonodeError("grad.sum_of_squares needs a uniform output grid t_eval (the fused objective's output cursor); for "
+                               "other grids use the materialised route: grad.solve, then the sum of squares of the current in torch")
+    cfg = dict(model=model, prot_v=prot_v, prot_t=prot_t, prot_t0=float(prot_t0), prot_dt=float(prot_dt), t_eval=t_eval,
+               prot_of_traj=None if prot_of_traj is None else torch.as_tensor(prot_of_traj, device=y0.device).to(torch.int32).contiguous(),
+               rtol=float(rtol), atol=float(atol), v_oob=float(v_oob), max_steps=int(max_steps), max_total_steps=int(max_total_steps),
+               max_step=float(max_step), obs_g=float(obs_g), obs_e=float(obs_e), obs_open_state_only=bool(obs_open_state_only),
+               t_eval_hint=hint, sse_ref=sse_ref, ckpt_cap=ckpt_cap, ckpt_budget_bytes=ckpt_budget_bytes)
+    return _SumOfSquares.apply(params, y0.contiguous(), cfg)

@@ -11,7 +11,7 @@ candidate's value on every rank); a scalar loss needs only `distributed.allreduc
 import numpy as np
 import torch
 
-from . import batched, capi, distributed
+from . import batched, capi, distributed, grad
 
 
 def population_sum_of_squares(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), prot_t0=0.0,
@@ -86,3 +86,78 @@ def population_sum_of_squares(candidates, protocols_v, data_i, t_eval, *, base_p
     parts = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(parts, pad, group=group)
     return torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
+
+
+def population_sum_of_squares_s1(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), prot_t0=0.0,
+                                 prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
+                                 obs_open_state_only=False, max_total_steps=1_000_000, max_step="auto", group=None, device=None,
+                                 solver=None, cost=None, model=capi.MODEL_HH2):
+    """Sum-of-squares error of every candidate AND its gradient with respect to the free parameters: the evaluateS1 counterpart
+    of population_sum_of_squares (PINTS SumOfSquaresError.evaluateS1, what PINTS' gradient-based optimisers call).
+
+    Arguments as population_sum_of_squares; model: HH 2-state (default, base_params [8]) or the 6-state model (base_params [12],
+    y0 of 6 states; obs_open_state_only=True observes the open state as train-d1.py:299).  Returns (sse [C] fp64,
+    dsse [C, len(free)] fp64) on the device; dsse[c, j] = d sse[c] / d candidates[c, j], the sum over the candidate's protocols of
+    the free columns of dL/dp (grad.sum_of_squares: fused forward + fused backward, no trace of size [C * P, Nt] is written).
+    A candidate any of whose solves failed gets sse = inf and a ZERO gradient row (the solve has no derivative there; an optimiser
+    that only compares values rejects it anyway).
+    max_step ("auto" by default: gradients through an uncapped solve are meaningless at equilibria, grad.solve): the "auto" cap
+    is grad.stable_step_cap over the WHOLE population (its finite candidates), computed before sharding -- a per-shard cap would
+    make every candidate's value depend on the world size.  Sharding as population_sum_of_squares (contiguous, or equal cost with `cost`); one
+    all-gather carries [C, 1 + len(free)].  `solver` (tests only): a stand-in with grad.sum_of_squares' signature, returning a
+    differentiable (sse, status), so the sharding / all-gather logic can run under gloo without a GPU.
+    """
+    import torch.distributed as dist
+    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
+        raise capi.IonodeError("population_sum_of_squares_s1: HH 2-state and 6-state models only")
+    D, npar = (6, 12) if model == capi.MODEL_MARKOV6 else (2, 8)
+    free = [int(f) for f in free]
+    cand = np.asarray(candidates, dtype=np.float64).reshape(-1, len(free))
+    C, P = cand.shape[0], np.asarray(protocols_v).shape[0]
+    base = np.asarray(base_params, dtype=np.float64)
+    if base.shape != (npar,) or len(y0) != D:
+        raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
+    on = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+    if cost is not None and len(cost) != C:
+        raise capi.IonodeError(f"cost has {len(cost)} entries for {C} candidates: the shards would not cover the population")
+    bounds = [distributed.shard_bounds(C, r, world) for r in range(world)] if cost is None \
+        else distributed.shard_bounds_by_cost(cost, world)
+    lo, hi = bounds[rank]
+    dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
+    solve = grad.sum_of_squares if solver is None else solver
+    params_all = np.tile(base, (C, 1))
+    params_all[:, free] = cand
+    if isinstance(max_step, str):
+        if max_step != "auto":
+            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
+        fin = np.isfinite(params_all).all(axis=1)   # (a non-finite candidate fails either way; it must not void everyone's cap)
+        max_step = grad.stable_step_cap(model, torch.from_numpy(params_all[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
+            if fin.any() else 0.0
+    nf = len(free)
+    out = torch.empty((hi - lo, 1 + nf), dtype=torch.float64, device=dev)
+    if hi > lo:
+        n = hi - lo
+        p = torch.from_numpy(np.repeat(params_all[lo:hi], P, axis=0)).to(dev).requires_grad_(True)   # trajectory = c * P + protocol
+        pot = torch.from_numpy(np.tile(np.arange(P, dtype=np.int32), n)).to(dev)
+        y0t = torch.tensor([list(y0)], dtype=state_dtype, device=dev).expand(n * P, D).contiguous()
+        sse, status = solve(model, p, torch.as_tensor(np.asarray(protocols_v), dtype=torch.float64, device=dev).contiguous(), y0t,
+                            torch.as_tensor(np.asarray(t_eval), dtype=torch.float64, device=dev).contiguous(),
+                            torch.as_tensor(np.asarray(data_i), dtype=torch.float64, device=dev).contiguous(),
+                            prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=pot, obs_g=obs_g, obs_e=obs_e,
+                            obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=max_step)
+        (gp,) = torch.autograd.grad(sse, p, grad_outputs=torch.ones_like(sse))
+        ok = (status.reshape(n, P) == 0).all(dim=1)
+        err = sse.detach().reshape(n, P).sum(dim=1)
+        gc = gp.reshape(n, P, npar).sum(dim=1)[:, free]
+        out[:, 0] = torch.where(ok, err, torch.full_like(err, float("inf")))
+        out[:, 1:] = torch.where(ok[:, None], gc, torch.zeros_like(gc))
+    if world > 1:
+        m = max(b[1] - b[0] for b in bounds)
+        pad = torch.zeros((m, 1 + nf), dtype=torch.float64, device=dev)
+        pad[:, 0] = float("inf")
+        pad[: hi - lo] = out
+        parts = [torch.empty_like(pad) for _ in range(world)]
+        dist.all_gather(parts, pad, group=group)
+        out = torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
+    return out[:, 0].contiguous(), out[:, 1:].contiguous()

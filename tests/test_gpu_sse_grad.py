@@ -1,0 +1,273 @@
+"""-m gpu: the fused sum-of-squares objective gradient (grad.sum_of_squares, ionode_dopri5_backward_sse,
+objective.population_sum_of_squares_s1) for the closed-form HH 2-state and 6-state models.  Checked against the fused forward of
+batched.solve (values), against the materialised route grad.solve -> torch current -> sum of squares -> autograd (gradients), and
+against autograd through the torch replay of the oracle's accepted steps (tests/grad_check.py)."""
+import ctypes as C
+import importlib
+
+import numpy as np
+import pytest
+import torch
+
+import kat_cases as K
+
+pytestmark = pytest.mark.gpu
+GRAD_REL_TOL = 1e-4     # fp32 state, and against the checker (as tests/test_gpu_grad.py)
+F64_TOL = 1e-9          # fp64 state, fused against materialised
+
+
+def _rel(a, b):
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
+
+
+def _obs(model):
+    # HH 2-state: gate = a * r, the reference's current (train-d0.py); 6-state: the open state, with a conductance
+    return dict(obs_g=1.0, obs_e=-86.0, obs_open_state_only=False) if model == K.MODEL_HH2 else \
+        dict(obs_g=0.7, obs_e=-86.0, obs_open_state_only=True)
+
+
+def _problem(model, B, seed, nan_row=None):
+    rng = np.random.default_rng(seed)
+    m6 = model == K.MODEL_MARKOV6
+    pv = np.stack([K.atau(30)[1][900:1300], K.atau(100)[1][900:1300], K.activation(20)[1][:400]])
+    te = np.arange(0.0, 140.0, 1.0)
+    params = np.tile(K.P_M6 if m6 else K.P_HH, (B, 1)) * rng.uniform(0.8, 1.25, (B, 12 if m6 else 8))
+    pot = rng.integers(0, 3, B).astype(np.int32)
+    y0 = np.stack([rng.uniform(0.0, 0.3, B), rng.uniform(0.6, 1.0, B)], 1)
+    if m6:
+        y0 = np.concatenate([y0, rng.uniform(0.0, 0.1, (B, 4))], 1)
+    if nan_row is not None:
+        y0[nan_row, 1] = np.nan
+    ref = rng.normal(0.0, 3.0, (3, te.size))
+    w = rng.uniform(0.5, 1.5, B)
+    return pv, te, params, pot, y0, ref, w
+
+
+def _dev(gpu, *xs):
+    return [None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(gpu) for x in xs]
+
+
+def _fused(ion, gpu, model, sdt, pv, te, params, pot, y0, ref, w, pt=None, cap=0.0):
+    pv_t, te_t, pot_t, ref_t, pt_t = _dev(gpu, pv, te, pot, ref, pt)
+    p = torch.from_numpy(params).to(gpu).requires_grad_(True)
+    y0t = torch.from_numpy(y0).to(gpu).to(sdt).requires_grad_(True)
+    sse, st = ion.grad.sum_of_squares(model, p, pv_t, y0t, te_t, ref_t, prot_t=pt_t, prot_t0=0.0, prot_dt=1.0, prot_of_traj=pot_t,
+                                      max_step=cap, **_obs(model))
+    gp, gy0 = torch.autograd.grad(sse, [p, y0t], grad_outputs=torch.from_numpy(w).to(gpu))   # failed rows: upstream ignored
+    return sse.detach().cpu().numpy(), st.cpu().numpy(), gp.cpu().numpy(), gy0.double().cpu().numpy()
+
+
+def _materialised(ion, gpu, model, sdt, pv, te, params, pot, y0, ref, w, pt=None, cap=0.0):
+    pv_t, te_t, pot_t, ref_t, pt_t = _dev(gpu, pv, te, pot, ref, pt)
+    p = torch.from_numpy(params).to(gpu).requires_grad_(True)
+    y0t = torch.from_numpy(y0).to(gpu).to(sdt).requires_grad_(True)
+    y, st = ion.grad.solve(model, None, p, pv_t, y0t, te_t, prot_t=pt_t, prot_t0=0.0, prot_dt=1.0, prot_of_traj=pot_t, max_step=cap)
+    o = _obs(model)
+    d = ion.capi.make_desc(n_out=te.size, n_prot=pv.shape[0], prot_n=pv.shape[1], prot_t0=0.0, prot_dt=1.0, v_oob=-80.0)
+    V = ion.capi.protocol_at_outputs(d, pv_t, pt_t, te_t)[pot_t.long()]                       # [B, Nt]
+    yd = y.double()
+    gate = yd[..., -1] if o["obs_open_state_only"] else yd[..., 0] * yd[..., 1]
+    i = o["obs_g"] * gate * (V - o["obs_e"])
+    ok = st == 0
+    per = ((i - ref_t[pot_t.long()]) ** 2).sum(1)
+    (torch.where(ok, per, torch.zeros_like(per)) * torch.from_numpy(w).to(gpu)).sum().backward()
+    return st.cpu().numpy(), p.grad.cpu().numpy(), y0t.grad.double().cpu().numpy()
+
+
+@pytest.mark.parametrize("f32", [False, True])
+@pytest.mark.parametrize("model", [K.MODEL_HH2, K.MODEL_MARKOV6])
+def test_fused_values_and_gradients(ion, gpu, model, f32):
+    """Values equal the fused forward of batched.solve; dL/dp and dL/dy0 equal the materialised route; a NaN y0 fails alone."""
+    B = 37
+    pv, te, params, pot, y0, ref, w = _problem(model, B, 7 + model + 2 * f32, nan_row=11)
+    sdt = torch.float32 if f32 else torch.float64
+    cap = ion.grad.stable_step_cap(model, torch.from_numpy(params), torch.from_numpy(pv))
+    rng = np.random.default_rng(3)
+    explicit = np.arange(400, dtype=np.float64) + np.concatenate([[0.0], rng.uniform(-1e-7, 1e-7, 399)])
+    for pt in (None, explicit):
+        sse, st, gp, gy0 = _fused(ion, gpu, model, sdt, pv, te, params, pot, y0, ref, w, pt, cap)
+        assert st[11] != 0 and (np.delete(st, 11) == 0).all()
+        assert np.isinf(sse[11]) and np.all(gp[11] == 0) and np.all(gy0[11] == 0)
+        pv_t, te_t, pot_t, ref_t, pt_t = _dev(gpu, pv, te, pot, ref, pt)
+        sol = ion.batched.solve(model, torch.from_numpy(params).to(gpu), pv_t, torch.from_numpy(y0).to(gpu).to(sdt), te_t,
+                                prot_t=pt_t, prot_t0=0.0, prot_dt=1.0, prot_of_traj=pot_t, sse_ref=ref_t, states=False,
+                                max_step=cap, **_obs(model))
+        want = sol.sse.cpu().numpy()
+        assert np.isinf(want[11])
+        ok = np.arange(B) != 11
+        assert np.all(np.abs(sse[ok] - want[ok]) <= 1e-12 * np.abs(want[ok])), np.max(np.abs(sse[ok] / want[ok] - 1))
+        # the failing trajectory leaves the others unchanged
+        y0v = y0.copy()
+        y0v[11, 1] = 0.8
+        sse2, st2, gp2, gy02 = _fused(ion, gpu, model, sdt, pv, te, params, pot, y0v, ref, w, pt, cap)
+        assert (st2 == 0).all()
+        assert np.array_equal(sse2[ok], sse[ok]) and np.array_equal(gp2[ok], gp[ok]) and np.array_equal(gy02[ok], gy0[ok])
+        # against the materialised route
+        stm, gpm, gy0m = _materialised(ion, gpu, model, sdt, pv, te, params, pot, y0, ref, w, pt, cap)
+        assert np.array_equal(stm, st)
+        tol = GRAD_REL_TOL if f32 else F64_TOL
+        e = (_rel(gp, gpm), _rel(gy0, gy0m))
+        print(f"model {model} {'f32' if f32 else 'f64'} {'explicit' if pt is not None else 'uniform'}: rel-L2 vs materialised "
+              f"dL/dp {e[0]:.2e} dL/dy0 {e[1]:.2e}")
+        assert max(e) <= tol, e
+
+
+@pytest.mark.parametrize("f32", [False, True])
+@pytest.mark.parametrize("model", [K.MODEL_HH2, K.MODEL_MARKOV6])
+def test_fused_gradients_against_the_checker(ion, gpu, oracle, model, f32):
+    """Every third trajectory: autograd through the torch replay of the oracle's accepted steps, SSE formed in torch."""
+    import grad_check as G
+    B = 37
+    pv, te, params, pot, y0, ref, w = _problem(model, B, 41 + model + 2 * f32)
+    if f32:
+        y0 = y0.astype(np.float32).astype(np.float64)
+    sdt = torch.float32 if f32 else torch.float64
+    cap = ion.grad.stable_step_cap(model, torch.from_numpy(params), torch.from_numpy(pv))
+    sse, st, gp, gy0 = _fused(ion, gpu, model, sdt, pv, te, params, pot, y0, ref, w, None, cap)
+    assert (st == 0).all()
+    o = _obs(model)
+    ptx = np.arange(400, dtype=np.float64)
+    pv_t, te_t = _dev(gpu, pv, te)
+    d = ion.capi.make_desc(n_out=te.size, n_prot=3, prot_n=400, prot_t0=0.0, prot_dt=1.0, v_oob=-80.0)
+    V = ion.capi.protocol_at_outputs(d, pv_t, None, te_t).cpu()
+    worst = 0.0
+    for b in range(0, B, 3):
+        r = oracle.solve(model, params[b], pv[pot[b]], y0[b], te, prot_t0=0.0, prot_dt=1.0, state_f32=f32, max_step=cap,
+                         step_log_cap=8192)
+        steps = G.accepted_steps(r["step_log"])
+        anchors = None
+        if f32:
+            ends = np.array([t0 + dt for t0, dt in steps])
+            anchors = oracle.solve(model, params[b], pv[pot[b]], y0[b], np.concatenate([[te[0]], ends]), prot_t0=0.0, prot_dt=1.0,
+                                   state_f32=True, max_step=cap)["y"][0][1:]
+        pb = torch.tensor(params[b], dtype=torch.float64, requires_grad=True)
+        yb = torch.tensor(y0[b], dtype=torch.float64, requires_grad=True)
+        yr = G.replay(model, None, 0, 0, pb, yb, ptx, pv[pot[b]], te, steps, f32_times=f32, anchors=anchors)
+        gate = yr[:, -1] if o["obs_open_state_only"] else yr[:, 0] * yr[:, 1]
+        i = o["obs_g"] * gate * (V[pot[b]] - o["obs_e"])
+        (w[b] * ((i - torch.from_numpy(ref[pot[b]])) ** 2).sum()).backward()
+        worst = max(worst, _rel(gp[b], pb.grad.numpy()), _rel(gy0[b], yb.grad.numpy()))
+    print(f"model {model} {'f32' if f32 else 'f64'}: worst rel-L2 vs checker {worst:.2e}")
+    assert worst <= GRAD_REL_TOL
+
+
+@pytest.mark.parametrize("model", [K.MODEL_HH2, K.MODEL_MARKOV6])
+def test_chunked_backward_is_bit_identical(ion, gpu, model):
+    """ionode_dopri5_backward_sse over [0, n_iter) in one launch and in three chunks (adjoint state carried in `state`); the
+    protocol-at-outputs table (ionode_desc.v_at_outputs) is read in both."""
+    capi = ion.capi
+    B = 37
+    pv, te, params, pot, y0, ref, w = _problem(model, B, 5)
+    pv_t, te_t, pot_t, ref_t, p_t, y0_t, w_t = _dev(gpu, pv, te, pot, ref, params, y0, w)
+    D = y0.shape[1]
+    npar = params.shape[1]
+    ckpt = torch.empty((B, 2048, 4 + 8 * D), dtype=torch.float64, device=gpu)
+    r = capi.dopri5(model, p_t, pv_t, y0_t, te_t, prot_t0=0.0, prot_dt=1.0, prot_of_traj=pot_t, ckpt=ckpt, sse_ref=ref_t,
+                    states=False, max_step=5.0, v_at_outputs=capi.protocol_at_outputs(capi.make_desc(
+                        n_out=te.size, n_prot=3, prot_n=400, prot_t0=0.0, prot_dt=1.0, v_oob=-80.0), pv_t, None, te_t), **_obs(model))
+    assert bool((r["status"] == 0).all()) and r["desc"].v_at_outputs
+    n_acc = r["stats"][:, 0].to(torch.int32).contiguous()
+    n_iter = int(n_acc.max()) + 1
+    assert n_iter <= 2048 and n_iter > 20
+    desc = r["desc"]
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    outs = []
+    for bounds in ([(0, n_iter)], [(0, 7), (7, 19), (19, n_iter)]):
+        state = torch.empty((B, 2 * D + npar), dtype=torch.float64, device=gpu)
+        gp = torch.zeros((B, npar), dtype=torch.float64, device=gpu)
+        gy0 = torch.zeros((B, D), dtype=torch.float64, device=gpu)
+        for it0, it1 in bounds:
+            rc = capi.lib().ionode_dopri5_backward_sse(C.byref(desc), it0, it1, n_iter, ptr(p_t), ptr(pv_t), None, ptr(pot_t),
+                                                       ptr(te_t), ptr(n_acc), ptr(w_t), ptr(state), ptr(gp), ptr(gy0),
+                                                       C.c_void_p(torch.cuda.current_stream(gpu).cuda_stream))
+            assert rc == 0, capi.lib().ionode_grad_last_error()
+        outs.append((gp.cpu(), gy0.cpu()))
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    assert bool(torch.isfinite(outs[0][0]).all()) and float(outs[0][0].abs().sum()) > 0
+
+
+@pytest.mark.parametrize("model", [K.MODEL_HH2, K.MODEL_MARKOV6])
+def test_64_per_wavefront_forward(ion, gpu, model):
+    """At ionode_lane_wise_from(model) trajectories the forward runs one trajectory per lane; the fused and materialised
+    gradients agree on sampled rows."""
+    B = int(ion.capi.lib().ionode_lane_wise_from(model, 0))
+    d = ion.capi.make_desc(model=model, n_state=6 if model == K.MODEL_MARKOV6 else 2, n_out=40, n_traj=B, n_prot=3, prot_n=400,
+                           n_params=12 if model == K.MODEL_MARKOV6 else 8, prot_dt=1.0, rtol=1e-7, atol=1e-9)
+    d.ckpt, d.ckpt_cap = 1, 1   # (a checkpointing launch: the dispatcher's general variant)
+    geo = {tw: (setattr(d, "tile_waves", tw), ion.capi.launch_geometry(d))[1] for tw in (64, 16, 0)}
+    assert geo[0] == geo[64] != geo[16]
+    pv, te, params, pot, y0, ref, w = _problem(model, B, 9)
+    te, ref = te[:40], ref[:, :40]
+    cap = ion.grad.stable_step_cap(model, torch.from_numpy(params), torch.from_numpy(pv))
+    sse, st, gp, gy0 = _fused(ion, gpu, model, torch.float64, pv, te, params, pot, y0, ref, w, None, cap)
+    stm, gpm, gy0m = _materialised(ion, gpu, model, torch.float64, pv, te, params, pot, y0, ref, w, None, cap)
+    assert (st == 0).all() and (stm == 0).all()
+    rows = np.random.default_rng(0).choice(B, 512, replace=False)
+    e = (_rel(gp[rows], gpm[rows]), _rel(gy0[rows], gy0m[rows]))
+    print(f"model {model}, B = {B}: rel-L2 vs materialised {e[0]:.2e} {e[1]:.2e}")
+    assert max(e) <= F64_TOL, e
+
+
+def test_memory_does_not_grow_with_the_output_grid(ion, gpu):
+    """HH 2-state fp64, 4096 x 100 001 samples: forward + backward peak below the checkpoints + 256 MiB (a [B, Nt, 2] trace alone
+    would be 6.5 GB)."""
+    B, Nt = 4096, 100001
+    rng = np.random.default_rng(2)
+    pv = ion.protocols.sinewave(ion.protocols.sinewave_scales(0, 4), n_samples=Nt, dt=0.1, xp=torch, device=gpu)
+    pot = (torch.arange(B, device=gpu) % 4).to(torch.int32)
+    te = torch.arange(Nt, dtype=torch.float64, device=gpu) * 0.1
+    params = torch.from_numpy(np.tile(K.P_HH, (B, 1)) * rng.uniform(0.9, 1.1, (B, 8))).to(gpu)
+    y0 = torch.tensor([[0.0, 1.0]], dtype=torch.float64, device=gpu).repeat(B, 1)
+    ref = torch.from_numpy(rng.normal(0.0, 1.0, (4, Nt))).to(gpu)
+    cap = ion.grad.stable_step_cap(K.MODEL_HH2, params, pv)
+    pre = ion.batched.solve(K.MODEL_HH2, params, pv, y0, te, prot_t0=0.0, prot_dt=0.1, prot_of_traj=pot, sse_ref=ref, states=False,
+                            max_step=cap)
+    most = int(pre.stats[:, 0].max())
+    del pre
+    ckpt_bytes = B * most * (4 + 8 * 2) * 8
+    torch.cuda.synchronize()
+    torch.cuda.reset_peak_memory_stats(gpu)
+    base = torch.cuda.memory_allocated(gpu)
+    p = params.clone().requires_grad_(True)
+    sse, st = ion.grad.sum_of_squares(K.MODEL_HH2, p, pv, y0, te, ref, prot_t0=0.0, prot_dt=0.1, prot_of_traj=pot, max_step=cap,
+                                      ckpt_cap=most)
+    sse.sum().backward()
+    torch.cuda.synchronize()
+    peak = torch.cuda.max_memory_allocated(gpu) - base
+    print(f"{most} accepted steps: checkpoints {ckpt_bytes / 2**30:.2f} GiB, peak {peak / 2**30:.2f} GiB")
+    assert bool((st == 0).all()) and bool(torch.isfinite(p.grad).all())
+    assert peak < ckpt_bytes + (256 << 20), (peak, ckpt_bytes)
+
+
+def test_population_s1_against_per_candidate_sums(ion, gpu):
+    """population_sum_of_squares_s1: values = per-candidate sums of grad.sum_of_squares, gradients = the materialised per-candidate
+    gradients, a failing candidate -> inf and a zero row."""
+    obj = importlib.import_module("neural-ode-ion-channels_amd.objective")
+    rng = np.random.default_rng(17)
+    C, free = 6, (0, 1, 2, 3)
+    cand = K.P_HH[None, :4] * rng.uniform(0.8, 1.25, (C, 4))
+    cand[4, 2] = np.nan
+    pv = np.stack([K.atau(30)[1][900:1300], K.atau(100)[1][900:1300], K.activation(20)[1][:400]])
+    te = np.arange(0.0, 140.0, 1.0)
+    data = rng.normal(0.0, 3.0, (3, te.size))
+    sse, g = obj.population_sum_of_squares_s1(cand, pv, data, te, base_params=K.P_HH, free=free, prot_t0=0.0, prot_dt=1.0,
+                                              state_dtype=torch.float64, device=gpu)
+    sse, g = sse.cpu().numpy(), g.cpu().numpy()
+    params = np.repeat(np.tile(K.P_HH, (C, 1)), 3, axis=0)
+    params[:, list(free)] = np.repeat(cand, 3, axis=0)
+    fin = np.isfinite(params).all(1)
+    cap = ion.grad.stable_step_cap(K.MODEL_HH2, torch.from_numpy(params[fin]), torch.from_numpy(pv))
+    pot = np.tile(np.arange(3, dtype=np.int32), C)
+    y0 = np.tile([0.0, 1.0], (3 * C, 1))
+    one = np.ones(3 * C)
+    s1, st1, _, _ = _fused(ion, gpu, K.MODEL_HH2, torch.float64, pv, te, params, pot, y0, data, one, None, cap)
+    stm, gpm, _ = _materialised(ion, gpu, K.MODEL_HH2, torch.float64, pv, te, params, pot, y0, data, one, None, cap)
+    want = s1.reshape(C, 3).sum(1)
+    ok = np.arange(C) != 4
+    assert np.isinf(sse[4]) and np.all(g[4] == 0) and (st1.reshape(C, 3)[4] != 0).any()
+    assert np.all(np.abs(sse[ok] - want[ok]) <= 1e-12 * np.abs(want[ok]))
+    gm = gpm.reshape(C, 3, 8).sum(1)[:, list(free)]
+    e = _rel(g[ok], gm[ok])
+    print(f"population S1: rel-L2 vs materialised {e:.2e}")
+    assert e <= F64_TOL
