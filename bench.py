@@ -8,10 +8,13 @@ y0 = [0, 1].  A "step" = one solve of the whole batch (one kernel launch) + the 
 epilogue + the loss reduction; with N > 1 GPUs every rank solves its own B trajectories (weak scaling,
 no data-path collective) and the scalar loss is all-reduced over RCCL.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--nt NT] [--no-cpu-baseline] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--nt NT] [--dump-outputs DIR] [--full [--no-cpu-baseline] ...]
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and `cpu_baseline`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes
+--dump-outputs and prints the line: the headline, its `config` and the `roofline` of the timed launches.  `--full` adds what takes
+work of its own: the CPU baselines (with the oracle parity check), the other kernels' legs, the counter-derived roofline figures
+from profiles/ and, with N > 1 ranks, the per-rank diagnostics and the sharded objective.
 """
 import argparse
 import importlib
@@ -57,12 +60,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--batch", type=int, default=4096, help="trajectories per GPU")
     ap.add_argument("--nt", type=int, default=100001, help="protocol samples = output samples")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="trajectories timed on the host (0 = auto)")
-    ap.add_argument("--no-python-baseline", action="store_true", help="skip the reference-structured Python leg")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the CPU baselines, the other kernels' legs, the counter-derived roofline "
+                         "figures and (N > 1 ranks) the per-rank diagnostics and the sharded objective; the flags below trim it")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: trajectories timed on the host (0 = auto)")
+    ap.add_argument("--no-python-baseline", action="store_true", help="--full: skip the reference-structured Python leg")
     ap.add_argument("--tile-waves", type=int, default=0)
     ap.add_argument("--no-extra-legs", action="store_true",
-                    help="skip the closed-form / gradient / regression measurements appended to the JSON line")
+                    help="--full: skip the closed-form / gradient / regression measurements appended to the JSON line")
     ap.add_argument("--stamps", action="store_true", help="diagnostic build (-DIONODE_STAMPS): print phase shares")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal)")
     ap.add_argument("--force-dist", action="store_true",
@@ -184,7 +190,7 @@ def main():
     # what a SCALE record needs to explain itself: every rank's own wall and kernel time (imbalance = device-to-device spread and step
     # counts, not communication) and the cost of the path's one collective, measured by itself after the timed region
     per_rank = None
-    if dist is not None:
+    if dist is not None and args.full:
         mine = torch.tensor([elapsed_own / args.steps * 1e3, kern_ms], dtype=torch.float64, device=dev)
         both = [torch.zeros_like(mine) for _ in range(world)]
         if args.dist_backend == "nccl":
@@ -251,7 +257,7 @@ def main():
             res["config"]["objective_sharded"] = {"error": repr(e)}
     lib_sha = capi.library_digest()
     res["config"]["libionode_sha256"] = lib_sha[:16]
-    pmc, pj_all = pmc_summary(lib_sha)
+    pmc, pj_all = pmc_summary(lib_sha) if args.full else (None, None)
     if pmc is not None and B == 4096 and Nt == 100001:
         # HBM bytes per launch from the rocprofv3 --pmc passes of this same command (profiles/README.md): FETCH_SIZE is
         # doubled (gfx950 counts 128-B requests as 64 B), WRITE_SIZE is exact; both are reported in KiB.  The counters belong
@@ -278,14 +284,14 @@ def main():
             res["roofline"]["valu_insts_per_mfma"] = None if stale else pj["pmc1"][kname]["SQ_INSTS_VALU"] / pj["pmc1"][kname]["SQ_INSTS_MFMA"] - 1.0
         except (KeyError, ValueError, ZeroDivisionError):
             pass
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(prot_v, weights, Nt, args.cpu_sample, out)
         if not args.no_python_baseline:
             try:
                 res["cpu_baseline_python"] = python_reference_structured_baseline(ion, prot_v, weights, Nt, out)
             except Exception as e:  # informational leg only
                 res["cpu_baseline_python"] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not args.no_extra_legs and B == 4096 and Nt == 100001:
+    if args.full and rank == 0 and world == 1 and not args.no_extra_legs and B == 4096 and Nt == 100001:
         # the other kernels of the path, measured in the same driver-run record: never part of `value`
         del r, prot_v, i_ref
         out.clear()

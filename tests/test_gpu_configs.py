@@ -166,7 +166,7 @@ def test_config4_full_population_properties(ion, gpu, oracle):
 
 def test_config2_full_batch_properties(ion, gpu):
     """BASELINE configs[1] at its full size -- 4096 NN-f s00 trajectories x 100 001 samples, fp64 state, fused current (the
-    bench.py workload; bench.py itself checks 512 of them against the oracle): the first 40 trajectories are the ones
+    bench.py workload; bench.py --full checks 512 of them against the oracle): the first 40 trajectories are the ones
     test_full_size_properties checks against the oracle and must come out bit-identical inside the full batch; trajectories
     that repeat another's inputs repeat its bits; a cost-sorted launch order changes nothing but the time."""
     import torch

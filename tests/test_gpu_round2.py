@@ -191,7 +191,7 @@ def test_runaway_candidate_is_bounded_and_isolated(ion, gpu, oracle):
 def test_bench_gpus_2_self_launches_two_ranks(ion, gpu):
     """`python bench.py --gpus 2` with no launcher starts two ranks itself (here both on this box's one GPU, gloo)."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--rehearse-on-one-gpu", "--dist-backend", "gloo",
-           "--batch", "64", "--nt", "5001", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--batch", "64", "--nt", "5001", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-2000:]

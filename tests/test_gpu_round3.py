@@ -351,7 +351,7 @@ def test_rccl_path_runs_under_the_drivers_launcher_with_one_rank(ion, gpu):
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--force-dist", "--batch", "64", "--nt", "5001",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra-legs"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-extra-legs"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env)

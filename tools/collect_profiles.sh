@@ -11,11 +11,11 @@ python3 -c "import importlib,sys; sys.path.insert(0,'.'); print(importlib.import
 # kernels' counters + summaries; no PART: everything
 PART=${PART:-12}
 if [[ $PART == *1* ]]; then
-python3 bench.py > $O/${R}_bench.json 2> $O/${R}_bench.err || exit 1
+python3 bench.py --full > $O/${R}_bench.json 2> $O/${R}_bench.err || exit 1
 # headline command alone (the s00 kernel's average launch duration must agree with the bench line's roofline.kernel_ms) ...
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-extra-legs > $O/${R}_bench_profiled.json 2> $O/trace.err || exit 1
 # ... and with the extra legs (closed-form, gradient, regression, launch order: the last re-uses the s00 kernel at 16384 trajectories)
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_legs -- python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline > $O/${R}_bench_profiled_legs.json 2> $O/trace_legs.err || exit 1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_legs -- python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline > $O/${R}_bench_profiled_legs.json 2> $O/trace_legs.err || exit 1
 S="--steps 1 --warmup 0 --no-cpu-baseline --no-extra-legs"
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $O/pmc1 -- python3 bench.py $S > /dev/null 2> $O/pmc1.err || exit 1
 rocprofv3 --pmc GRBM_GUI_ACTIVE FETCH_SIZE --output-format csv -d $O/pmc2 -- python3 bench.py $S > /dev/null 2> $O/pmc2.err || exit 1
