@@ -15,6 +15,16 @@ import kat_cases as K
 pytestmark = pytest.mark.gpu
 
 
+def step_protocols(rng, P, Np):
+    """Random step protocols [P, Np]: 3-7 plateaus between -120 and +60 mV (also drawn by tests/sse_cases.py)."""
+    pv = np.empty((P, Np))
+    for p in range(P):
+        edges = np.sort(rng.choice(np.arange(5, Np - 5), size=int(rng.integers(2, 6)), replace=False))
+        levels = rng.uniform(-120, 60, edges.size + 1)
+        pv[p] = levels[np.searchsorted(edges, np.arange(Np), side="right")]
+    return pv
+
+
 def _case(seed):
     rng = np.random.default_rng(1000 + seed)
     model = [K.MODEL_HH2, K.MODEL_MARKOV6, K.MODEL_NNF, K.MODEL_NND][seed % 4]
@@ -23,12 +33,7 @@ def _case(seed):
     P = int(rng.choice([1, 2, 5]))
     Np = int(rng.integers(150, 400))
     dt = float(rng.choice([0.5, 1.0, 2.0]))
-    # random step protocols: 3-7 plateaus between -120 and +60 mV
-    pv = np.empty((P, Np))
-    for p in range(P):
-        edges = np.sort(rng.choice(np.arange(5, Np - 5), size=int(rng.integers(2, 6)), replace=False))
-        levels = rng.uniform(-120, 60, edges.size + 1)
-        pv[p] = levels[np.searchsorted(edges, np.arange(Np), side="right")]
+    pv = step_protocols(rng, P, Np)
     explicit = bool(rng.integers(0, 3) == 0)
     t0 = float(rng.choice([0.0, 10.0]))
     pt = t0 + np.cumsum(rng.uniform(0.5, 1.5, Np) * dt) if explicit else None

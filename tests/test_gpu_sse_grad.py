@@ -117,7 +117,7 @@ def test_fused_values_and_gradients(ion, gpu, model, f32):
 @pytest.mark.parametrize("model", [K.MODEL_HH2, K.MODEL_MARKOV6])
 def test_fused_gradients_against_the_checker(ion, gpu, oracle, model, f32):
     """Every third trajectory: autograd through the torch replay of the oracle's accepted steps, SSE formed in torch."""
-    import grad_check as G
+    import sse_cases as S
     B = 37
     pv, te, params, pot, y0, ref, w = _problem(model, B, 41 + model + 2 * f32)
     if f32:
@@ -126,28 +126,12 @@ def test_fused_gradients_against_the_checker(ion, gpu, oracle, model, f32):
     cap = ion.grad.stable_step_cap(model, torch.from_numpy(params), torch.from_numpy(pv))
     sse, st, gp, gy0 = _fused(ion, gpu, model, sdt, pv, te, params, pot, y0, ref, w, None, cap)
     assert (st == 0).all()
-    o = _obs(model)
-    ptx = np.arange(400, dtype=np.float64)
-    pv_t, te_t = _dev(gpu, pv, te)
-    d = ion.capi.make_desc(n_out=te.size, n_prot=3, prot_n=400, prot_t0=0.0, prot_dt=1.0, v_oob=-80.0)
-    V = ion.capi.protocol_at_outputs(d, pv_t, None, te_t).cpu()
+    c = S.SimpleNamespace(model=model, f32=f32, B=B, P=3, pv=pv, prot_t=None, prot_t0=0.0, prot_dt=1.0, te=te, params=params, y0=y0,
+                          pot=pot, rtol=1e-7, atol=1e-9, max_steps=0, max_total_steps=0, max_step=cap, obs=_obs(model), ref=ref, w=w)
     worst = 0.0
     for b in range(0, B, 3):
-        r = oracle.solve(model, params[b], pv[pot[b]], y0[b], te, prot_t0=0.0, prot_dt=1.0, state_f32=f32, max_step=cap,
-                         step_log_cap=8192)
-        steps = G.accepted_steps(r["step_log"])
-        anchors = None
-        if f32:
-            ends = np.array([t0 + dt for t0, dt in steps])
-            anchors = oracle.solve(model, params[b], pv[pot[b]], y0[b], np.concatenate([[te[0]], ends]), prot_t0=0.0, prot_dt=1.0,
-                                   state_f32=True, max_step=cap)["y"][0][1:]
-        pb = torch.tensor(params[b], dtype=torch.float64, requires_grad=True)
-        yb = torch.tensor(y0[b], dtype=torch.float64, requires_grad=True)
-        yr = G.replay(model, None, 0, 0, pb, yb, ptx, pv[pot[b]], te, steps, f32_times=f32, anchors=anchors)
-        gate = yr[:, -1] if o["obs_open_state_only"] else yr[:, 0] * yr[:, 1]
-        i = o["obs_g"] * gate * (V[pot[b]] - o["obs_e"])
-        (w[b] * ((i - torch.from_numpy(ref[pot[b]])) ** 2).sum()).backward()
-        worst = max(worst, _rel(gp[b], pb.grad.numpy()), _rel(gy0[b], yb.grad.numpy()))
+        wp, wy = S.reference_gradient(oracle, c, b)   # (the replay of the oracle's accepted steps, SSE in torch fp64, autograd)
+        worst = max(worst, _rel(gp[b], wp), _rel(gy0[b], wy))
     print(f"model {model} {'f32' if f32 else 'f64'}: worst rel-L2 vs checker {worst:.2e}")
     assert worst <= GRAD_REL_TOL
 
