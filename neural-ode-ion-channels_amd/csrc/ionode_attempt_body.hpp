@@ -314,16 +314,13 @@
       // 8 consecutive samples as before, partial sum number = chunk number -- which is why steps of more than 64 samples take the
       // one-trajectory-per-pass loop below); V(t_k) and the reference current of the NEXT pass are loaded before this pass's stores.
       bool packed_lane = false;   // my trajectory's samples are emitted by the work-list passes (the others: the loop below)
-      if constexpr (LW && (VTAB || D > 2 || (CF2 && TAIL == 1))) {
+      if constexpr (LW && (VTAB || D > 2 || (CF2 && F::lean == Lean::States))) {
         // a chunk of PK = 8 samples is served by PKL lanes x NSL samples each (lane kk: samples kk, kk + PKL, ...): one row read per
         // NSL samples -- with one sample per lane the LDS pipe, not the vector ALU, bounded these passes (the 6-state row is 272 bytes)
-#ifndef IONODE_PACK_PKL_D6
-#define IONODE_PACK_PKL_D6 2
-#endif
-        constexpr int PK = 8, PKL = (D == 2) ? 4 : IONODE_PACK_PKL_D6, NSL = PK / PKL;
+        constexpr int PK = 8, PKL = (D == 2) ? 4 : 2, NSL = PK / PKL;
         typedef S SV __attribute__((ext_vector_type(NSL)));
         const bool want_i = (a.i_out != nullptr) || (a.sse_out != nullptr);
-        // one instance per compiled variant: the table variant (TAIL == 2) serves the current / objective epilogue, the plain one
+        // one instance per compiled variant: the table variant serves the current / objective epilogue, the plain one
         // states only (its epilogue without the table -- a protocol lookup per sample -- stays on the loop below)
         // (2-state kernels that also store the states keep the loop below: at ~34 samples per step its 64 consecutive samples per
         // store instruction touch half the cache lines of 8 x 8, and that path is store-bound: 41.5 against 44.7 ms packed)

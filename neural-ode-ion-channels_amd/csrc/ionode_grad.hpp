@@ -73,9 +73,6 @@ __host__ __device__ constexpr size_t grad_img_fwd(int L, int NT) { return grad_i
 __host__ __device__ constexpr size_t grad_img_bwd(int L, int NT) { return grad_img_fwd(L, NT) + (size_t)L * NT * NT * 256; }
 __host__ __device__ constexpr size_t grad_img_floats(int L, int NT) { return grad_img_bwd(L, NT) + (size_t)L * NT * NT * 256; }
 
-#ifndef IONODE_GRAD_OWN0
-#define IONODE_GRAD_OWN0 1
-#endif
 template <int NT>
 struct GradMlp {
   static constexpr int G = 4;
@@ -226,7 +223,7 @@ struct GradMlp {
   // to wait for it (the fold of the previous product's remainder tile) -- runs BEHIND step 0's MFMAs, so the LDS round trip
   // and the wait for the slowest wavefront overlap with them (the forward kernel's arrangement, ionode_device.hpp).  Widths
   // without a full tile per wavefront (N <= 48) run `after0` first and read every operand from LDS.
-  static constexpr bool OWN0 = (F >= 1) && IONODE_GRAD_OWN0;
+  static constexpr bool OWN0 = (F >= 1);
   // SCHED: what may cross the end of a k-tile step in hipcc's scheduler (sched_barrier mask).  0: nothing -- the refills stay where
   // they are issued.  (0xF -- ALU and MFMA may, memory operations may not -- gained 3.5 % where only backward products ran and
   // loses 5.8 % on the regression step: 1.94 -> 2.05 ms.)

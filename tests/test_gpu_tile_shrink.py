@@ -1,5 +1,5 @@
 """-m gpu, round 6: the lean N = 200 16-tile finishes its tiles on the 4-trajectory net once <= 4 of their trajectories are live
-(MlpShrink4, ionode_device.hpp).  Only the net changes: every case returns the oracle's bits, and the same bits with the switch turned
+(MlpShrink4, ionode_mlp_tile4.hpp).  Only the net changes: every case returns the oracle's bits, and the same bits with the switch turned
 off (IONODE_TILE_SHRINK=0, read per plan -- a fresh child process runs every case that way)."""
 import json
 import os

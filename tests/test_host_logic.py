@@ -455,3 +455,27 @@ def test_every_width_up_to_512_has_a_kernel_and_an_image(ion):
     with pytest.raises(capi.IonodeError):
         capi.mlp_pack(np.zeros(2 * 600 + 600 + 600 + 1, dtype=np.float32), 0, 600)
     assert capi.kernel_name(capi.make_desc(mlp_width=64, tile_waves=1, **kw)) == ""   # the generic tile is a four-wavefront tile
+
+
+def test_dispatch_table_and_images_are_pinned(ion):
+    """tests/golden/dispatch_table.json (tests/golden/make_dispatch_fixture.py): for ~1 000 descriptors the dispatcher's return code, kernel
+    variant, launch geometry and error text, and the SHA-256 of ionode_mlp_pack's image for ten seeded nets, recorded from the library as it was
+    before the kernel-form decoder replaced the hand-written slot decoding and ionode_mlp_pack became one packer per image section -- a change to the planner or the packer that moves any of
+    them has to regenerate the fixture on purpose.  Every compiled variant is in the table at least once (asserted by the generator)."""
+    import importlib.util
+    import json
+    golden = os.path.join(os.path.dirname(__file__), "golden")
+    spec = importlib.util.spec_from_file_location("make_dispatch_fixture", os.path.join(golden, "make_dispatch_fixture.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    doc = json.load(open(os.path.join(golden, "dispatch_table.json")))
+    assert doc["contracts"] == list(gen.CONTRACTS) and doc["columns"][:8] == list(gen.COLUMNS)
+    assert len(doc["rows"]) > 900 and set(range(1, len(doc["kernels"]))) <= {r[9] for r in doc["rows"]}
+    for r in doc["rows"]:
+        row = tuple(r[:7]) + (doc["contracts"][r[7]],)
+        rc, geo, name, err = gen.replay_row(ion.capi, row)
+        want = (r[8], r[11:15] or None, doc["kernels"][r[9]], doc["errors"][r[10]])
+        assert (rc, geo, name, err) == want, row
+    assert [tuple(p[:2]) for p in doc["packs"]] == list(gen.PACK_SHAPES)
+    for L, N, floats, sha in doc["packs"]:
+        assert gen.pack_digest(ion.capi, L, N) == (floats, sha), (L, N)

@@ -4,7 +4,7 @@
     python3 tools/gen_mlp_asm.py --nt 13 --pd 7 --ns 1 --out neural-ode-ion-channels_amd/csrc/mlp_asm_nt13.inc
     python3 tools/gen_mlp_asm.py --nt 13 --pd 7 --ns 2 --out neural-ode-ion-channels_amd/csrc/mlp_asm_nt13x2.inc
 
-What it emits (consumed by MlpTile in csrc/ionode_device.hpp): two C string macros (suffix <NT> or <NT>x<NS>),
+What it emits (consumed by MlpTile in csrc/ionode_mlp_tile.hpp): two C string macros (suffix <NT> or <NT>x<NS>),
 
     IONODE_MLPASM_INIT_*    prime the weight ring with hidden layer 0 (kernel start)
     IONODE_MLPASM_LAYERS_*  one whole evaluation net([x0, x1]) of the tile: Linear(2, N) + LeakyReLU on the VALU, for
@@ -17,7 +17,7 @@ FLOP -- and wavefronts 0, 1 carry the Runge-Kutta state of column set 0, wavefro
 integrator work is replicated twice instead of four times per trajectory.  The stage inputs are exchanged through LDS; the
 result is returned for the wavefront's own set.
 
-The arithmetic is the canonical accumulation order of ionode_device.hpp (MlpTile::eval): every accumulator's chain visits
+The arithmetic is the canonical accumulation order of ionode_mlp_tile.hpp (MlpTile::eval): every accumulator's chain visits
 the same (k-tile, k-step) sequence, so the bits do not change; what changes is the order in which INDEPENDENT
 accumulators are interleaved, where the epilogue sits, and who allocates the registers:
 

@@ -1,5 +1,5 @@
 """Dev tool: where the lean N = 200 16-tile's attempts ran -- on its own net or, once <= 4 of a tile's trajectories were live, on the
-4-trajectory net (MlpShrink4, ionode_device.hpp) -- read from the step log of the diagnostic build:
+4-trajectory net (MlpShrink4, ionode_mlp_tile4.hpp) -- read from the step log of the diagnostic build:
 
   tools/build_variant.sh stamps -DIONODE_STAMPS
   IONODE_LIB=neural-ode-ion-channels_amd/variants/stamps/libionode.so python tools/tile_shrink_stamps.py [--batch 4096] [--nt 100001]
