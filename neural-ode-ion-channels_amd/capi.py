@@ -53,6 +53,11 @@ class IonodeError(RuntimeError):
     pass
 
 
+def ckpt_record_doubles(D):
+    """fp64 words of one accepted-step checkpoint record [t0, dt, oi, nout, y[D], k1..k7[D]] (csrc/ionode_grad_step.hpp CkptRecord)."""
+    return 4 + 8 * D
+
+
 def build(force=False, jobs=8):
     """Compile libionode.so for gfx950 with hipcc (cross-compiles without a GPU)."""
     csrc = os.path.join(_HERE, "csrc")
@@ -277,8 +282,8 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
     if launch_order is not None:
         _dev_ptr(launch_order, torch.int32, "launch_order", (B,))
         desc.launch_order = launch_order.data_ptr()
-    if ckpt is not None:  # [B, cap, 4 + 8*D] f64 device tensor: accepted-step records for the backward sweep
-        _dev_ptr(ckpt, torch.float64, "ckpt", (B, ckpt.shape[1], 4 + 8 * D))
+    if ckpt is not None:  # [B, cap, record] f64 device tensor: accepted-step records for the backward sweep
+        _dev_ptr(ckpt, torch.float64, "ckpt", (B, ckpt.shape[1], ckpt_record_doubles(D)))
         desc.ckpt = ckpt.data_ptr()
         desc.ckpt_cap = ckpt.shape[1]
     if step_log is not None:  # [cap, 4] f64 device tensor: (t0, dt, ratio, accepted) per attempt of trajectory 0

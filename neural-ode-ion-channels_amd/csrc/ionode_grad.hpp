@@ -26,46 +26,34 @@
 // it does not fit) and a second kernel (ionode_grad_reduce, whole chip, split-K fp32 MFMA GEMM) contracts them.
 #pragma once
 
-#include "ionode_device.hpp"
+#include <type_traits>
+
+#include "ionode_grad_step.hpp"   // GArgs and the layouts of the streams between the launches
 
 namespace ionode {
 
-struct GArgs {
-  KArgs k;                 // protocol lookup fields (prot_t, Np, prot_t0, prot_dt, v_oob), params, prot_v, prot_of_traj, t_eval, B, Nt, P, L, N, NP, NT
-  const float *img;        // grad image (ionode_grad_pack)
-  const double *ckpt;      // [B][ckpt_cap][4 + 8*D] accepted-step records of the forward launch
-  const int32_t *nacc;     // [B] accepted steps to replay (0: nothing to differentiate, e.g. a failed trajectory)
-  const void *grad_y;      // [B][Nt][D] dL/dy_out in the state dtype
-  double *state;           // [B][GRAD_STATE] adjoint state carried between chunk launches: lam[2], mu[2], gp[8]
-  float *records;          // [n_tiles][it_end - it_begin][6][record_floats] (d, h) stream for ionode_grad_reduce, or NULL
-  double *grad_params;     // [B][8]   written by the launch with it_end == n_iter
-  double *grad_y0;         // [B][2]
-  int32_t ckpt_cap, it_begin, it_end, n_iter;
-  int64_t record_floats;
-  double *packets;            // two-phase sweep: the adjoint-independent scalars of every (tile, step): [n_tiles][it_end - it_begin][16][GRAD_PACKET] fp64
-  int32_t phase;              // 0: one-phase sweep; 1: phase A (recompute kernel); 2: phase B (walk kernel)
-  // fused sum-of-squares seed (ionode_dopri5_backward_sse_kernel; grad_y unused): dL/dy_k is formed in the kernel from
-  // dL/dsse[b] and the residual of sample k against sse_ref -- no [B][Nt][D] gradient exists
-  const double *grad_sse;     // [B] upstream dL/dsse
-  const double *sse_ref;      // [P][Nt] reference currents
-  const double *v_tab;        // optional [P][Nt] V(t_k) (ionode_protocol_at_outputs), or NULL: protocol_v per sample
-  double obs_g, obs_e;
-  int32_t obs_open;
-};
-constexpr int GRAD_SIGN_WORDS = 8;   // 64-bit words per lane and evaluation (Signs below)
-// packet of one trajectory and step (doubles): [0] dts, [1] step, [2] initev, [4 + c*2 + d] G_c (interpolant-coefficient adjoint
-// sums), [16 + 8 e + {0..6}] stage e: V, Y_i[0], Y_i[1], exp(p6 V), exp(-p8 V), exp(p2 V), exp(-p4 V)
-constexpr int GRAD_PACKET = 64;
-
-constexpr int GRAD_STATE = 12;
-
-// floats of one tile-evaluation record: H_0..H_L, D_0..D_L (NT tiles of 64 lanes x float4 each) + 64 scalars (x0, x1, seed, pad) x 16
-__host__ __device__ constexpr int64_t grad_record_floats(int L, int NT) { return (int64_t)2 * (L + 1) * NT * 256 + 64; }
 __host__ __device__ constexpr size_t grad_lds_bytes(int L, int NT) {
   // two activation buffers + two gradient buffers (ping-pong over the layers, whatever L is) + remainder partial sums + small vectors
   // (+ the input layer's second weight column as a contiguous vector: the closing dot product d net / d x1)
   return ((size_t)4 * NT * 64 + (size_t)2 * (NT % 4) * 4 * 64 + 16 * NT) * 16 + ((size_t)L * 16 * NT + 16 * NT + 4) * 4 + 16 * 10 * 8 + (NT <= 13 ? (size_t)16 * NT * 4 : 0);   // (N = 500 with 10 layers fills the 160 KiB without it)
 }
+// One call per compiled width NT = N padded to 16, 112, 208 or 512 (architectures/s00-s11.py: N = 10, 100, 200, 500):
+// f(std::integral_constant<int, NT>) for the units' own widths, f32() for N = 500 (instantiated in inst_grad32.hip); false: no such variant.
+template <typename F, typename F32> bool for_width(int NT, F f, F32 f32) {
+  switch (NT) {
+    case 1: f(std::integral_constant<int, 1>{}); return true;
+    case 7: f(std::integral_constant<int, 7>{}); return true;
+    case 13: f(std::integral_constant<int, 13>{}); return true;
+    case 32: f32(); return true;
+    default: return false;
+  }
+}
+
+template <typename Kern> void raise_lds_limit(Kern kern, size_t lds) {
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+}
+
 // image offsets (floats): rows of layer 0 {b0, w00, w01, 0} | hidden biases | wl, bl | forward fragments | transposed fragments
 __host__ __device__ constexpr size_t grad_img_bias(int NT) { return (size_t)4 * 16 * NT; }
 __host__ __device__ constexpr size_t grad_img_wl(int L, int NT) { return grad_img_bias(NT) + (size_t)L * 16 * NT; }
@@ -486,8 +474,8 @@ struct GradMlp {
     const float pair = part + __shfl_xor(part, 16);
     const float out = pair + __shfl_xor(pair, 32);
     if (rec && wave == 0 && lane < 16) {
-      float *sc = rec + (size_t)2 * (L + 1) * NT * 256;
-      sc[lane] = x0; sc[16 + lane] = x1; sc[32 + lane] = seed; sc[48 + lane] = 0.0f;
+      float *sc = rec + IONODE_RECORD_SCALARS(L, NT);
+      sc[REC_X0 + lane] = x0; sc[REC_X1 + lane] = x1; sc[REC_SEED + lane] = seed; sc[REC_PAD + lane] = 0.0f;
     }
     __syncthreads();  // the next evaluation's layer 0 rewrites Hs[0] / Ds
     return out;
@@ -564,7 +552,8 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
   const int pidx = a.k.prot_of_traj ? a.k.prot_of_traj[traj] : (traj % a.k.P);
   const double *__restrict__ pv = a.k.prot_v + (size_t)pidx * a.k.Np;
   const int nst = valid ? a.nacc[traj] : 0;
-  const int RECW = 4 + 8 * D;
+  using CK = CkptRecord<D>;
+  constexpr int RECW = CK::WIDTH;
   const double *__restrict__ ck = a.ckpt + (size_t)traj * a.ckpt_cap * RECW;
   const int Nt = a.k.Nt;
   const bool pk_writer = wave == 0 && lane < 16;
@@ -575,12 +564,12 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
   // one in front of every stage's product -- about a dozen exposed round trips.  Now: the NEXT iteration's checkpoint is fetched while this
   // one's products run, the four trajectories' first 64 samples are loaded together, and the stage voltages are looked up ahead of the
   // stages (as the forward kernel does): three round trips.  Same values, same summation order, same bits.
-  double crec[4 + 8 * D];   // the coming iteration's checkpoint record (a clamped, always valid row: what is not wanted is masked below)
+  double crec[RECW];   // the coming iteration's checkpoint record (a clamped, always valid row: what is not wanted is masked below)
   auto fetch_ckpt = [&](int it) {
     const int s = nst - 1 - it;
     const double *rec = ck + (size_t)(s >= 0 ? s : 0) * RECW;
 #pragma unroll
-    for (int i = 0; i < 4 + 8 * D; ++i) crec[i] = rec[i];
+    for (int i = 0; i < RECW; ++i) crec[i] = rec[i];
   };
   constexpr bool CKPT_AHEAD = NT > 13 || IONODE_RECOMPUTE_WG_PER_CU < 2;   // (two workgroups per unit: the other one covers the round trip, and the 40 registers are not there)
   if (CKPT_AHEAD && it_lo < it_hi) fetch_ckpt(it_lo);
@@ -594,14 +583,14 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
     int oi = 0, nout = 0;
     {
       const bool ld = step || initev;
-      if (ld) { t0 = crec[0]; dt = crec[1]; }
-      if (step) { oi = (int)crec[2]; nout = (int)crec[3]; }
+      if (ld) { t0 = crec[CK::T0]; dt = crec[CK::DT]; }
+      if (step) { oi = (int)crec[CK::OI]; nout = (int)crec[CK::NOUT]; }
 #pragma unroll
-      for (int d = 0; d < D; ++d) y[d] = ld ? crec[4 + d] : 0.0;
+      for (int d = 0; d < D; ++d) y[d] = ld ? crec[CK::Y + d] : 0.0;
 #pragma unroll
       for (int jx = 0; jx < 7; ++jx)
 #pragma unroll
-        for (int d = 0; d < D; ++d) k[jx][d] = step ? crec[4 + D + jx * D + d] : 0.0;
+        for (int d = 0; d < D; ++d) k[jx][d] = step ? crec[CK::K + jx * D + d] : 0.0;
     }
     if (CKPT_AHEAD && it + 1 < it_hi) fetch_ckpt(it + 1);
     const double t1 = t0 + dt;
@@ -610,7 +599,8 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
     const size_t tstep = (size_t)blockIdx.x * (a.it_end - a.it_begin) + (it - a.it_begin);
     double *__restrict__ pk = a.packets + (tstep * 16 + j) * GRAD_PACKET;
 
-    // ---- adjoints of the interpolant coefficients: G_c = sum_k gy[k] * x_k^c over the step's output samples (verbatim) ----
+    // ---- adjoints of the interpolant coefficients: G_c = sum_k gy[k] * x_k^c over the step's output samples ----
+    // (a copy of ionode_grad_sweep_body.hpp's reduction: a shared routine compiled to other code -- DESIGN_HISTORY.md, "The backward sweep's step algebra"; correct both)
     // (the first 64 samples of the wavefront's four trajectories: all loads in flight before the first is used)
     double tk0[4] = {0.0, 0.0, 0.0, 0.0};
     S gy0[4][D] = {};
@@ -671,11 +661,11 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
     }
     __syncthreads();
     if (pk_writer) {
-      pk[0] = dts; pk[1] = step ? 1.0 : 0.0; pk[2] = initev ? 1.0 : 0.0; pk[3] = 0.0;
+      pk[pkt::DTS] = dts; pk[pkt::STEP] = step ? 1.0 : 0.0; pk[pkt::INITEV] = initev ? 1.0 : 0.0; pk[3] = 0.0;
 #pragma unroll
       for (int c = 0; c < 5; ++c)
 #pragma unroll
-        for (int d = 0; d < D; ++d) pk[4 + c * D + d] = Gs[j * (5 * D) + c * D + d];
+        for (int d = 0; d < D; ++d) pk[pkt::GC + c * D + d] = Gs[j * (5 * D) + c * D + d];
     }
     // ---- the six stages' scalar work, AHEAD of their products (round 5): stage voltages (pure functions of (t0, dt): the five distinct
     // lookups in flight together -- stage i = 5 shares i = 4's time), stage inputs Y_i, rate exponentials, the packet; what a product needs
@@ -715,8 +705,8 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
         double e1 = 0.0, e2 = 0.0;
         if constexpr (NND) { e1 = det_exp(p[1] * v); e2 = det_exp(-p[3] * v); }
         if (pk_writer) {
-          double *q8 = pk + 16 + 8 * e;
-          q8[0] = v; q8[1] = Yi[0]; q8[2] = Yi[1]; q8[3] = e3; q8[4] = e4; q8[5] = e1; q8[6] = e2;
+          double *q8 = pk + pkt::STAGE + pkt::STAGE_W * e;
+          q8[pkt::V] = v; q8[pkt::Y0] = Yi[0]; q8[pkt::Y1] = Yi[1]; q8[pkt::E3] = e3; q8[pkt::E4] = e4; q8[pkt::E1] = e1; q8[pkt::E2] = e2;
           xs[(e * 16 + j) * 2] = x0; xs[(e * 16 + j) * 2 + 1] = x1;
         }
       }
@@ -728,7 +718,7 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
       // the WHOLE vector-Jacobian product with seed 1 (it is linear in the seed, a scalar per trajectory): record with unit-seed
       // D tiles, and c = d net / d x1 for the walk
       const float c1 = mlp.template vjp<false>(xx[0], xx[1], 1.0f, a.records ? a.records + (tstep * 6 + e) * a.record_floats : nullptr);
-      if (pk_writer) pk[16 + 8 * e + 7] = (double)c1;
+      if (pk_writer) pk[pkt::STAGE + pkt::STAGE_W * e + pkt::C] = (double)c1;
     }
   }
 }
@@ -764,7 +754,7 @@ __global__ void __launch_bounds__(64) ionode_grad_walk_kernel(const GArgs a) {
 #pragma unroll
     for (int i = 0; i < NPAR; ++i) gp[i] = a.it_begin > 0 ? st[2 * D + i] : 0.0;
   }
-  const size_t sc_off = (size_t)2 * (a.k.L + 1) * a.k.NT * 256 + 32;   // the seeds inside a record's scalar block
+  const size_t sc_off = IONODE_RECORD_SCALARS(a.k.L, a.k.NT) + REC_SEED;   // the seeds inside a record's scalar block
   const double2 *__restrict__ psrc = reinterpret_cast<const double2 *>(a.packets + (size_t)blockIdx.x * (a.it_end - a.it_begin) * 16 * GRAD_PACKET) + 8 * lane;
   for (int it = a.it_begin; it < a.it_end; ++it) {
     const size_t tstep = (size_t)blockIdx.x * (a.it_end - a.it_begin) + (it - a.it_begin);
@@ -777,15 +767,16 @@ __global__ void __launch_bounds__(64) ionode_grad_walk_kernel(const GArgs a) {
     }
     __syncthreads();
     const double *__restrict__ pk = pkl + j * GRAD_PACKET;
-    const double dts = pk[0];
-    const bool step = pk[1] != 0.0, initev = pk[2] != 0.0;
+    const double dts = pk[pkt::DTS];
+    const bool step = pk[pkt::STEP] != 0.0, initev = pk[pkt::INITEV] != 0.0;
     double Gc[5][D];
 #pragma unroll
     for (int c = 0; c < 5; ++c)
 #pragma unroll
-      for (int d = 0; d < D; ++d) Gc[c][d] = pk[4 + c * D + d];
+      for (int d = 0; d < D; ++d) Gc[c][d] = pk[pkt::GC + c * D + d];
 
-    // ---- interpolant adjoint -> (Y0, Y1, k1..k7); FSAL carry (as in the one-phase kernel) ----
+    // ---- interpolant adjoint -> (Y0, Y1, k1..k7); FSAL carry ----
+    // (a copy of ionode_grad_sweep_body.hpp's: shared, the kernels compiled to other code -- DESIGN_HISTORY.md, "The backward sweep's step algebra"; correct both)
     double aY0[D], aY1[D], ak[7][D];
 #pragma unroll
     for (int d = 0; d < D; ++d) {
@@ -803,15 +794,15 @@ __global__ void __launch_bounds__(64) ionode_grad_walk_kernel(const GArgs a) {
     auto stage = [&](auto ec) {
       constexpr int e = decltype(ec)::value;
       constexpr int i = 5 - e;
-      const double *__restrict__ q8 = pk + 16 + 8 * e;
-      const double v = q8[0], av = q8[1], rv = q8[2], e3 = q8[3], e4 = q8[4];
+      const double *__restrict__ q8 = pk + pkt::STAGE + pkt::STAGE_W * e;
+      const double v = q8[pkt::V], av = q8[pkt::Y0], rv = q8[pkt::Y1], e3 = q8[pkt::E3], e4 = q8[pkt::E4];
       double seed[D];
 #pragma unroll
       for (int d = 0; d < D; ++d) seed[d] = step ? ak[i + 1][d] : ((initev && e == 0) ? mu[d] : 0.0);
       const float seedf = (float)(seed[0] / 1000.0);
       if (rec_it && lane < 16) rec_it[(size_t)e * a.record_floats + sc_off + lane] = seedf;
-      const float dx1 = seedf * (float)q8[7];
-      // closed-form terms of the RHS and their parameter gradients (the one-phase kernel's expressions)
+      const float dx1 = seedf * (float)q8[pkt::C];
+      // closed-form terms of the RHS and their parameter gradients (copies of ionode_grad_sweep_body.hpp's stage terms and propagation, for the same reason; correct both)
       double w[D];
       const double k3 = p[4] * e3, k4 = p[6] * e4;
       w[0] = (double)dx1;
@@ -821,7 +812,7 @@ __global__ void __launch_bounds__(64) ionode_grad_walk_kernel(const GArgs a) {
       gp[6] += seed[1] * (e4 * (1.0 - rv));
       gp[7] += seed[1] * (-k4 * v * (1.0 - rv));
       if constexpr (NND) {
-        const double e1 = q8[5], e2 = q8[6];
+        const double e1 = q8[pkt::E1], e2 = q8[pkt::E2];
         const double k1 = p[0] * e1, k2 = p[2] * e2;
         w[0] += -seed[0] * (k1 + k2);
         gp[0] += seed[0] * (e1 * (1.0 - av));

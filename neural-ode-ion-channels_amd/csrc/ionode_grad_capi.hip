@@ -13,19 +13,56 @@ void gerr(const char *m) { snprintf(g_gerr, sizeof g_gerr, "%s", m); }
 
 inline int np_of(int N) { return 16 * ((N + 15) / 16); }
 
+using ionode::GArgs;
+using ionode::Sweep;
 using ionode::SweepFn;
-using ionode::pick_sweep;
-using ionode::launch_sweep;
 
-// the widths of architectures/s00-s11.py: N = 10, 100, 200, 500
-SweepFn find_sweep(int model, int f32, int NT) {
-  switch (NT) {
-    case 1: return pick_sweep<1>(model, f32);
-    case 7: return pick_sweep<7>(model, f32);
-    case 13: return pick_sweep<13>(model, f32);
-    case 32: return ionode::pick_sweep32(model, f32);   // inst_grad32.hip
-    default: return nullptr;
+// launchers that have no width: the closed-form models' sweeps (NT = 1, unused) and the NN models' walk
+template <int MODEL> SweepFn closed_sweep(int f32) { return f32 ? &ionode::launch_sweep<MODEL, float, 1> : &ionode::launch_sweep<MODEL, double, 1>; }
+template <int MODEL> SweepFn closed_sweep_sse(int f32) { return f32 ? &ionode::launch_sweep_sse<MODEL, float> : &ionode::launch_sweep_sse<MODEL, double>; }
+template <int MODEL> SweepFn walk(int f32) { return f32 ? &ionode::launch_walk<MODEL, float> : &ionode::launch_walk<MODEL, double>; }
+
+// nullptr: no variant of that width (a width without a sweep has no walk either, though the walk kernel itself has no width)
+SweepFn find_sweep(Sweep which, int model, int f32, int NT) {
+  if (which == Sweep::Walk) {
+    if (!ionode::for_width(NT, [](auto) {}, [] {})) return nullptr;
+    return model == IONODE_MODEL_NNF ? walk<IONODE_MODEL_NNF>(f32) : walk<IONODE_MODEL_NND>(f32);
   }
+  const bool recompute = which == Sweep::Recompute;
+  SweepFn fn = nullptr;
+  ionode::for_width(NT, [&](auto nt) { fn = ionode::pick_sweep<decltype(nt)::value>(recompute, model, f32); },
+                    [&] { fn = ionode::pick_sweep32(recompute, model, f32); });   // inst_grad32.hip
+  return fn;
+}
+
+// ---- what every sweep entry point shares: the descriptor's consistency, and the argument block filled from it ----
+inline bool is_m6(const ionode_desc *d) { return d->model == IONODE_MODEL_MARKOV6; }
+inline bool desc_consistent(const ionode_desc *d) {
+  const bool m6 = is_m6(d);
+  return !(d->n_state != (m6 ? 6 : 2) || d->n_traj < 1 || d->n_out < 1 || d->n_prot < 1 || d->prot_n < 2 || d->n_params < (m6 ? 12 : 8) || !(d->prot_dt > 0));
+}
+inline bool bad_range(int32_t it_begin, int32_t it_end, int32_t n_iter) { return it_begin < 0 || it_end <= it_begin || it_end > n_iter; }
+
+// (L, NP): the net; closed-form models: (0, 16)
+GArgs fill_args(const ionode_desc *d, int L, int NP, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *params,
+                const double *prot_v, const double *prot_t, const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
+                double *state, double *grad_params, double *grad_y0) {
+  GArgs a;
+  memset(&a, 0, sizeof a);
+  a.k.params = params; a.k.prot_v = prot_v; a.k.prot_t = prot_t; a.k.prot_of_traj = prot_of_traj; a.k.t_eval = t_eval;
+  a.k.B = d->n_traj; a.k.Nt = d->n_out; a.k.P = d->n_prot; a.k.Np = d->prot_n; a.k.n_params = d->n_params;
+  a.k.L = L; a.k.NP = NP; a.k.NT = NP / 16;
+  a.k.prot_t0 = d->prot_t0; a.k.prot_dt = d->prot_dt; a.k.prot_rdt = 1.0 / d->prot_dt; a.k.v_oob = d->v_oob;
+  a.ckpt = d->ckpt; a.ckpt_cap = d->ckpt_cap; a.nacc = n_accepted; a.state = state; a.grad_params = grad_params; a.grad_y0 = grad_y0;
+  a.it_begin = it_begin; a.it_end = it_end; a.n_iter = n_iter;
+  return a;
+}
+
+int launch(SweepFn fn, const GArgs &a, size_t lds, void *stream) {
+  fn(a, (unsigned)((a.k.B + 15) / 16), lds, reinterpret_cast<hipStream_t>(stream));
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { gerr(hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
+  return IONODE_OK;
 }
 
 }  // namespace
@@ -82,68 +119,54 @@ int ionode_grad_pack(const float *w, int32_t L, int32_t N, float *out) {
   return IONODE_OK;
 }
 
-// mode 0: one-phase sweep; 1: phase A (forward recompute of every (tile, step), records + sign words); 2: phase B (the walk)
-static int backward_impl(int mode, const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
+// One-phase sweep, or phase A (Recompute: the unit-seed products and packets of every (tile, step)) / phase B (Walk) of the two-phase
+// sweep.  Phase A carries no adjoint state: it requires neither `state` nor the gradient outputs.
+static int backward_impl(Sweep which, const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
                          const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                          const double *t_eval, const int32_t *n_accepted, const void *grad_y, double *state,
                          float *records, double *packets, double *grad_params, double *grad_y0, void *stream) {
   if (!d) { gerr("null descriptor"); return IONODE_ERR_ARG; }
-  if (mode != 0 && (!packets || (d->model != IONODE_MODEL_NNF && d->model != IONODE_MODEL_NND))) {
+  const bool two_phase = which != Sweep::OnePhase;
+  if (two_phase && (!packets || (d->model != IONODE_MODEL_NNF && d->model != IONODE_MODEL_NND))) {
     gerr("two-phase sweep: NN-f / NN-d only, `packets` required"); return IONODE_ERR_ARG;
   }
-  if (mode == 1) {   // phase A carries no adjoint state: stand-ins so that the shared checks pass (never dereferenced)
-    static double dummy;
-    state = &dummy; grad_params = &dummy; grad_y0 = &dummy;
-  }
-  const bool m6 = d->model == IONODE_MODEL_MARKOV6;
-  const bool hh2 = d->model == IONODE_MODEL_HH2 || m6;  // closed-form models: no MLP image, no records
+  const bool m6 = is_m6(d);
+  const bool closed = d->model == IONODE_MODEL_HH2 || m6;  // closed-form models: no MLP image, no records
   if (d->model < 0 || d->model > 3) { gerr("backward sweep: unknown model"); return IONODE_ERR_UNSUPPORTED; }
-  if (d->n_state != (m6 ? 6 : 2) || d->n_traj < 1 || d->n_out < 1 || d->n_prot < 1 || d->prot_n < 2 || d->n_params < (m6 ? 12 : 8) || !(d->prot_dt > 0)) {
-    gerr("inconsistent descriptor"); return IONODE_ERR_ARG;
-  }
-  if ((!grad_image && !hh2) || !params || !prot_v || !t_eval || !n_accepted || !grad_y || !state || !grad_params || !grad_y0 || !d->ckpt || d->ckpt_cap < 1) {
+  if (!desc_consistent(d)) { gerr("inconsistent descriptor"); return IONODE_ERR_ARG; }
+  const bool adjoint = which != Sweep::Recompute;   // the launch reads and writes the adjoint state
+  if ((!grad_image && !closed) || !params || !prot_v || !t_eval || !n_accepted || !grad_y || (adjoint && (!state || !grad_params || !grad_y0)) || !d->ckpt || d->ckpt_cap < 1) {
     gerr("ionode_dopri5_backward: required buffer is NULL (ckpt / ckpt_cap come from the descriptor)"); return IONODE_ERR_ARG;
   }
-  if (it_begin < 0 || it_end <= it_begin || it_end > n_iter) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
-  if (mode == 1 && (int64_t)it_end - it_begin > (int64_t)65535 * ionode::GRAD_RECOMPUTE_IB) {
+  if (bad_range(it_begin, it_end, n_iter)) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
+  if (which == Sweep::Recompute && (int64_t)it_end - it_begin > (int64_t)65535 * ionode::GRAD_RECOMPUTE_IB) {
     gerr("ionode_dopri5_backward_recompute: at most 65535 x 4 iterations per launch (HIP's grid.y limit): split the range");
     return IONODE_ERR_ARG;
   }
   if (d->traj_per_image > 0) { gerr("backward sweep: one weight set per launch (traj_per_image must be 0)"); return IONODE_ERR_UNSUPPORTED; }
-  if (!hh2 && (d->mlp_layers < 1 || d->mlp_width < 1)) { gerr("bad MLP shape"); return IONODE_ERR_ARG; }
-  const int NP = hh2 ? 16 : np_of(d->mlp_width), NT = NP / 16, L = hh2 ? 0 : d->mlp_layers;
-  SweepFn fn = m6 ? (d->state_f32 ? &launch_sweep<IONODE_MODEL_MARKOV6, float, 1> : &launch_sweep<IONODE_MODEL_MARKOV6, double, 1>)
-               : hh2 ? (d->state_f32 ? &launch_sweep<IONODE_MODEL_HH2, float, 1> : &launch_sweep<IONODE_MODEL_HH2, double, 1>)
-                     : find_sweep(d->model, d->state_f32 ? 1 : 0, NT);
-  const size_t lds = hh2 ? (size_t)16 * 5 * (m6 ? 6 : 2) * 8 : ionode::grad_lds_bytes(L, NT);
+  if (!closed && (d->mlp_layers < 1 || d->mlp_width < 1)) { gerr("bad MLP shape"); return IONODE_ERR_ARG; }
+  const int NP = closed ? 16 : np_of(d->mlp_width), NT = NP / 16, L = closed ? 0 : d->mlp_layers;
+  SweepFn fn = m6 ? closed_sweep<IONODE_MODEL_MARKOV6>(d->state_f32) : closed ? closed_sweep<IONODE_MODEL_HH2>(d->state_f32)
+                                                                            : find_sweep(which, d->model, d->state_f32 ? 1 : 0, NT);
+  const size_t lds = closed ? ionode::grad_closed_lds_bytes(d->n_state) : ionode::grad_lds_bytes(L, NT);
   if (!fn || lds > 160 * 1024 || L > 15) {
     gerr("backward sweep: (L, N) outside the compiled variants (N pads to 16, 112, 208 or 512; at most 15 hidden layers)");
     return IONODE_ERR_UNSUPPORTED;
   }
-  ionode::GArgs a;
-  memset(&a, 0, sizeof a);
-  a.k.params = params; a.k.prot_v = prot_v; a.k.prot_t = prot_t; a.k.prot_of_traj = prot_of_traj; a.k.t_eval = t_eval;
-  a.k.B = d->n_traj; a.k.Nt = d->n_out; a.k.P = d->n_prot; a.k.Np = d->prot_n; a.k.n_params = d->n_params;
-  a.k.L = L; a.k.N = d->mlp_width; a.k.NP = NP; a.k.NT = NT;
-  a.k.prot_t0 = d->prot_t0; a.k.prot_dt = d->prot_dt; a.k.prot_rdt = 1.0 / d->prot_dt; a.k.v_oob = d->v_oob;
-  a.img = grad_image; a.ckpt = d->ckpt; a.ckpt_cap = d->ckpt_cap; a.nacc = n_accepted; a.grad_y = grad_y; a.state = state;
-  a.records = hh2 ? nullptr : records; a.grad_params = grad_params; a.grad_y0 = grad_y0;
-  a.it_begin = it_begin; a.it_end = it_end; a.n_iter = n_iter;
+  GArgs a = fill_args(d, L, NP, it_begin, it_end, n_iter, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, state, grad_params, grad_y0);
+  a.k.N = d->mlp_width; a.img = grad_image; a.grad_y = grad_y;
+  a.records = closed ? nullptr : records;
   a.record_floats = ionode::grad_record_floats(L, NT);
-  a.packets = mode != 0 ? packets : nullptr;
-  a.phase = mode;
-  if (mode != 0 && ionode::grad_lds_bytes(L, NT) + 16 + 16 * ionode::GRAD_PACKET * 8 > 160 * 1024) { gerr("two-phase sweep: LDS"); return IONODE_ERR_UNSUPPORTED; }
-  fn(a, (unsigned)((d->n_traj + 15) / 16), lds, reinterpret_cast<hipStream_t>(stream));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { gerr(hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
-  return IONODE_OK;
+  a.packets = two_phase ? packets : nullptr;
+  if (two_phase && ionode::grad_lds_bytes(L, NT) + 16 + ionode::grad_walk_lds_bytes() > 160 * 1024) { gerr("two-phase sweep: LDS"); return IONODE_ERR_UNSUPPORTED; }
+  return launch(fn, a, lds, stream);
 }
 
 int ionode_dopri5_backward(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
                            const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                            const double *t_eval, const int32_t *n_accepted, const void *grad_y, double *state,
                            float *records, double *grad_params, double *grad_y0, void *stream) {
-  return backward_impl(0, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
+  return backward_impl(Sweep::OnePhase, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
                        state, records, nullptr, grad_params, grad_y0, stream);
 }
 
@@ -156,30 +179,16 @@ int ionode_dopri5_backward_sse(const ionode_desc *d, int32_t it_begin, int32_t i
     gerr("ionode_dopri5_backward_sse: closed-form models only (HH 2-state, 6-state)"); return IONODE_ERR_UNSUPPORTED;
   }
   if (d->traj_per_image > 0) { gerr("ionode_dopri5_backward_sse: traj_per_image must be 0"); return IONODE_ERR_UNSUPPORTED; }
-  const bool m6 = d->model == IONODE_MODEL_MARKOV6;
-  if (d->n_state != (m6 ? 6 : 2) || d->n_traj < 1 || d->n_out < 1 || d->n_prot < 1 || d->prot_n < 2 || d->n_params < (m6 ? 12 : 8) || !(d->prot_dt > 0)) {
-    gerr("inconsistent descriptor"); return IONODE_ERR_ARG;
-  }
+  if (!desc_consistent(d)) { gerr("inconsistent descriptor"); return IONODE_ERR_ARG; }
   if (!d->sse_ref || !grad_sse || !d->ckpt || d->ckpt_cap < 1 || !params || !prot_v || !t_eval || !n_accepted || !state || !grad_params || !grad_y0) {
     gerr("ionode_dopri5_backward_sse: required buffer is NULL (sse_ref / ckpt / ckpt_cap come from the descriptor)"); return IONODE_ERR_ARG;
   }
-  if (it_begin < 0 || it_end <= it_begin || it_end > n_iter) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
-  ionode::GArgs a;
-  memset(&a, 0, sizeof a);
-  a.k.params = params; a.k.prot_v = prot_v; a.k.prot_t = prot_t; a.k.prot_of_traj = prot_of_traj; a.k.t_eval = t_eval;
-  a.k.B = d->n_traj; a.k.Nt = d->n_out; a.k.P = d->n_prot; a.k.Np = d->prot_n; a.k.n_params = d->n_params;
-  a.k.NP = 16; a.k.NT = 1;
-  a.k.prot_t0 = d->prot_t0; a.k.prot_dt = d->prot_dt; a.k.prot_rdt = 1.0 / d->prot_dt; a.k.v_oob = d->v_oob;
-  a.ckpt = d->ckpt; a.ckpt_cap = d->ckpt_cap; a.nacc = n_accepted; a.state = state; a.grad_params = grad_params; a.grad_y0 = grad_y0;
-  a.it_begin = it_begin; a.it_end = it_end; a.n_iter = n_iter;
+  if (bad_range(it_begin, it_end, n_iter)) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
+  GArgs a = fill_args(d, 0, 16, it_begin, it_end, n_iter, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, state, grad_params, grad_y0);
   a.grad_sse = grad_sse; a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
   a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
-  SweepFn fn = m6 ? (d->state_f32 ? &ionode::launch_sweep_sse<IONODE_MODEL_MARKOV6, float> : &ionode::launch_sweep_sse<IONODE_MODEL_MARKOV6, double>)
-                  : (d->state_f32 ? &ionode::launch_sweep_sse<IONODE_MODEL_HH2, float> : &ionode::launch_sweep_sse<IONODE_MODEL_HH2, double>);
-  fn(a, (unsigned)((d->n_traj + 15) / 16), (size_t)16 * 5 * (m6 ? 6 : 2) * 8, reinterpret_cast<hipStream_t>(stream));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { gerr(hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
-  return IONODE_OK;
+  SweepFn fn = is_m6(d) ? closed_sweep_sse<IONODE_MODEL_MARKOV6>(d->state_f32) : closed_sweep_sse<IONODE_MODEL_HH2>(d->state_f32);
+  return launch(fn, a, ionode::grad_closed_lds_bytes(d->n_state), stream);
 }
 
 size_t ionode_grad_packet_doubles(void) { return (size_t)16 * ionode::GRAD_PACKET; }
@@ -188,7 +197,7 @@ int ionode_dopri5_backward_recompute(const ionode_desc *d, int32_t it_begin, int
                                      const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                                      const double *t_eval, const int32_t *n_accepted, const void *grad_y, float *records,
                                      double *packets, void *stream) {
-  return backward_impl(1, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
+  return backward_impl(Sweep::Recompute, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
                        nullptr, records, packets, nullptr, nullptr, stream);
 }
 
@@ -197,7 +206,7 @@ int ionode_dopri5_backward_sweep(const ionode_desc *d, int32_t it_begin, int32_t
                                  const double *t_eval, const int32_t *n_accepted, const void *grad_y, double *state,
                                  float *records, const double *packets, double *grad_params, double *grad_y0,
                                  void *stream) {
-  return backward_impl(2, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
+  return backward_impl(Sweep::Walk, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
                        state, records, const_cast<double *>(packets), grad_params, grad_y0, stream);
 }
 
@@ -244,12 +253,9 @@ int ionode_regress_step(int32_t L, int32_t N, const float *grad_image, const flo
   a.img = grad_image; a.x = x; a.y = y; a.offset = offset; a.records = records; a.loss_part = loss_partials;
   a.M = n_rows; a.L = L; a.N = N; a.NT = NT; a.record_floats = ionode::grad_record_floats(L, NT); a.netscale = netscale;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (NT) {
-    case 1: ionode::launch_regress<1>(a, (unsigned)n_workgroups, s); break;
-    case 7: ionode::launch_regress<7>(a, (unsigned)n_workgroups, s); break;
-    case 13: ionode::launch_regress<13>(a, (unsigned)n_workgroups, s); break;
-    case 32: ionode::launch_regress32(a, (unsigned)n_workgroups, s); break;
-    default: gerr("ionode_regress_step: width outside the compiled variants (N pads to 16, 112, 208 or 512)"); return IONODE_ERR_UNSUPPORTED;
+  if (!ionode::for_width(NT, [&](auto nt) { ionode::launch_regress<decltype(nt)::value>(a, (unsigned)n_workgroups, s); },
+                         [&] { ionode::launch_regress32(a, (unsigned)n_workgroups, s); })) {
+    gerr("ionode_regress_step: width outside the compiled variants (N pads to 16, 112, 208 or 512)"); return IONODE_ERR_UNSUPPORTED;
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { gerr(hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }

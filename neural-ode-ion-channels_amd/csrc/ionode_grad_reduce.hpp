@@ -85,14 +85,14 @@ __global__ void __launch_bounds__(256, grad_reduce_wg_per_cu(NT)) ionode_grad_re
           const int64_t rr = (rb + u < r1) ? rb + u : r1 - 1;   // (past the end: a valid record, its contribution is skipped below)
           const float *rec = records + rr * RECF;
           const f32x4 *tiles = reinterpret_cast<const f32x4 *>(rec) + (size_t)(first ? (L + 1) * NT : L * NT) * 64;  // D_0 | H_L
-          const float *sc = rec + (size_t)2 * (L + 1) * NT * 256;
+          const float *sc = rec + IONODE_RECORD_SCALARS(L, NT);
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
-            s0[u][c] = first ? sc[4 * c + kk] : sc[32 + 4 * c + kk];  // x0 | seed
-            s1[u][c] = first ? sc[16 + 4 * c + kk] : 0.0f;            // x1
-            sd[u][c] = sc[32 + 4 * c + kk];
+            s0[u][c] = first ? sc[REC_X0 + 4 * c + kk] : sc[REC_SEED + 4 * c + kk];
+            s1[u][c] = first ? sc[REC_X1 + 4 * c + kk] : 0.0f;
+            sd[u][c] = sc[REC_SEED + 4 * c + kk];
           }
-          sgl[u] = (lane < 16) ? sc[32 + lane] : 0.0f;
+          sgl[u] = (lane < 16) ? sc[REC_SEED + lane] : 0.0f;
 #pragma unroll
           for (int i = 0; i < RCL; ++i) {
             const int rt = wave + 4 * i;
@@ -177,7 +177,7 @@ __global__ void __launch_bounds__(256, grad_reduce_wg_per_cu(NT)) ionode_grad_re
   // from global memory in the iteration that uses them (rounds 3-5) their wait was `s_waitcnt vmcnt(0)` in front of the record's first
   // MFMA, which also waited for the NEXT record's staging loads -- every record paid a full memory round trip, with or without seeds.
   float *seedbuf = reinterpret_cast<float *>(buf + (size_t)2 * STE);   // [2][16]
-  auto seed_src = [&](int64_t rr) -> const float * { return records + rr * RECF + (size_t)2 * (L + 1) * NT * 256 + 32 + (threadIdx.x & 15); };
+  auto seed_src = [&](int64_t rr) -> const float * { return records + rr * RECF + IONODE_RECORD_SCALARS(L, NT) + REC_SEED + (threadIdx.x & 15); };
   float sdg = 1.0f;
   if (r0 < r1) {
 #pragma unroll
@@ -288,24 +288,20 @@ inline int grad_reduce_slabs(int L, int NT, int cus, int64_t n_records) {
   return n < 1 ? 1 : (int)n;
 }
 
+#ifndef IONODE_GRAD_TEMPLATES_ONLY  // (one unit launches, and with that instantiates, the reduce kernels)
 inline hipError_t launch_grad_reduce(int L, int NT, const float *records, int64_t n_records, int n_slabs, float *partials,
                                      hipStream_t s, int unit_seed = 0) {
   const int CB = grad_reduce_cb(NT), NCB = grad_reduce_ncb(NT);
   const unsigned grid = (unsigned)(n_slabs * (L * NCB + 1));
   const size_t lds = (size_t)2 * (NT + CB) * 64 * 16 + 128;   // tile buffers + the staged seeds
-  switch (NT) {
-    case 1: hipLaunchKernelGGL(ionode_grad_reduce_kernel<1>, dim3(grid), dim3(256), lds, s, records, n_records, n_slabs, L, partials, unit_seed); break;
-    case 7: hipLaunchKernelGGL(ionode_grad_reduce_kernel<7>, dim3(grid), dim3(256), lds, s, records, n_records, n_slabs, L, partials, unit_seed); break;
-    case 13: hipLaunchKernelGGL(ionode_grad_reduce_kernel<13>, dim3(grid), dim3(256), lds, s, records, n_records, n_slabs, L, partials, unit_seed); break;
-    case 32: {
-      auto kern = ionode_grad_reduce_kernel<32>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, records, n_records, n_slabs, L, partials, unit_seed);
-      break;
-    }
-    default: return hipErrorInvalidValue;
-  }
+  auto launch = [&](auto nt) {
+    auto kern = ionode_grad_reduce_kernel<decltype(nt)::value>;
+    raise_lds_limit(kern, lds);   // (N = 500: 80 KiB)
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, records, n_records, n_slabs, L, partials, unit_seed);
+  };
+  if (!for_width(NT, launch, [&] { launch(std::integral_constant<int, 32>{}); })) return hipErrorInvalidValue;
   return hipGetLastError();
 }
+#endif
 
 }  // namespace ionode

@@ -2,6 +2,9 @@
 // ionode_dopri5_backward_kernel (SSE = false: output gradients read from grad_y) and ionode_dopri5_backward_sse_kernel (SSE = true:
 // the fused sum-of-squares seed).  It reads the kernel's `a`, MODEL, S, NT and SSE.  Included rather than called, so that the
 // grad_y kernels compile to the code they had before the fused variant existed.
+// The checkpoint load, the G_c reduction and the stage input stand a second time in ionode_grad_recompute_kernel; the interpolant
+// adjoint, the 2-state stage terms, the stage propagation and the adjoint state's load and store in ionode_grad_walk_kernel.  Shared
+// routines compiled to other code (DESIGN_HISTORY.md, "The backward sweep's step algebra"), so a correction here is made there too.
   constexpr int D = ModelTraits<MODEL>::D, NPAR = ModelTraits<MODEL>::NPAR;
   static_assert(!SSE || !ModelTraits<MODEL>::MLP, "the fused sum-of-squares sweep is built for the closed-form models");
   constexpr bool M6 = MODEL == IONODE_MODEL_MARKOV6;  // 6-state model (train-d1.py:165-187): f = M(rates(V)) y, closed form
@@ -33,12 +36,13 @@
   const int pidx = a.k.prot_of_traj ? a.k.prot_of_traj[traj] : (traj % a.k.P);
   const double *__restrict__ pv = a.k.prot_v + (size_t)pidx * a.k.Np;
   const int nst = valid ? a.nacc[traj] : 0;
-  const int RECW = 4 + 8 * D;
+  using CK = CkptRecord<D>;
+  constexpr int RECW = CK::WIDTH, RECY = CK::Y;
   const double *__restrict__ ck = a.ckpt + (size_t)traj * a.ckpt_cap * RECW;
   const S *__restrict__ gy = SSE ? nullptr : reinterpret_cast<const S *>(a.grad_y) + (size_t)traj * a.k.Nt * D;
   const int Nt = a.k.Nt;
 
-  constexpr int STATE = 2 * D + NPAR;  // adjoint state carried between chunk launches (== GRAD_STATE for the 2-state models)
+  constexpr int STATE = 2 * D + NPAR;  // adjoint state carried between chunk launches
   double lam[D], mu[D], gp[NPAR];
   {
     const double *st = a.state + (size_t)traj * STATE;
@@ -58,14 +62,14 @@
     {
       const double *rec = ck + (size_t)(step ? s : 0) * RECW;
       const bool ld = step || initev;
-      if (ld) { t0 = rec[0]; dt = rec[1]; }
-      if (step) { oi = (int)rec[2]; nout = (int)rec[3]; }
+      if (ld) { t0 = rec[CK::T0]; dt = rec[CK::DT]; }
+      if (step) { oi = (int)rec[CK::OI]; nout = (int)rec[CK::NOUT]; }
 #pragma unroll
-      for (int d = 0; d < D; ++d) y[d] = ld ? rec[4 + d] : 0.0;
+      for (int d = 0; d < D; ++d) y[d] = ld ? rec[CK::Y + d] : 0.0;
 #pragma unroll
       for (int jx = 0; jx < 7; ++jx)
 #pragma unroll
-        for (int d = 0; d < D; ++d) k[jx][d] = step ? rec[4 + D + jx * D + d] : 0.0;
+        for (int d = 0; d < D; ++d) k[jx][d] = step ? rec[CK::K + jx * D + d] : 0.0;
     }
     const double t1 = t0 + dt;
     const S t0s = (S)t0, dts_s = (S)dt, t1s = (S)t1;
@@ -85,7 +89,7 @@
       if (step && s + 1 < nst) {
         const double *rec1 = ck + (size_t)(s + 1) * RECW;
 #pragma unroll
-        for (int d = 0; d < D; ++d) y1[d] = (S)rec1[4 + d];
+        for (int d = 0; d < D; ++d) y1[d] = (S)rec1[RECY + d];
       } else {
         S bd[6];
 #pragma unroll
@@ -353,7 +357,7 @@
         if (nst > 0) {
           S y0s[D];
 #pragma unroll
-          for (int d = 0; d < D; ++d) y0s[d] = (S)ck[4 + d];
+          for (int d = 0; d < D; ++d) y0s[d] = (S)ck[RECY + d];
           double v0;
           if (a.v_tab) v0 = a.v_tab[(size_t)pidx * Nt];
           else protocol_v(a.k, pv, a.k.t_eval[0], v0);

@@ -7,6 +7,7 @@
 namespace ionode {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 // Dormand-Prince / Shampine coefficients.
 __device__ constexpr double kAlpha[6] = {1.0 / 5, 3.0 / 10, 4.0 / 5, 8.0 / 9, 1.0, 1.0};

@@ -23,7 +23,6 @@ namespace ionode {
 // layer and row pair, PB floats: {W[2m][k], W[2m+1][k]} in the canonical k order, {bias, bias'}, pad.
 // ---------------------------------------------------------------------------------------------
 // (GP = 5 row pairs of a hidden layer evaluated together (scalar loads of the group in flight at once, independent chains): 65 536 x 20 001: 15.5 ms at 1, 14.3 at 2, 14.2 at 3, 13.6 at 5; 262 144: 38.4 / 36.6 / 36.6 / 36.0)
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 // acc + w * h.lo / acc + w * h.hi in both halves (one fused multiply-add each); w: SGPR pair
 __device__ __forceinline__ f32x2 pk_fma_lo(f32x2 w, f32x2 h, f32x2 acc) {
   asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(acc) : "s"(w), "v"(h));

@@ -73,6 +73,75 @@ def stable_step_cap(model, params, prot_v, v_oob=-80.0, safety=3.0):
     return safety / lam_max if lam_max > 0 and np.isfinite(lam_max) else 0.0
 
 
+def _forward_with_checkpoints(launch, B, D, cfg, dev):
+    """Forward solve with accepted-step checkpoints: `launch(ckpt)` runs capi.dopri5 with the caller's keywords on a [B, cap, record]
+    buffer, which is sized by ckpt_cap / ckpt_budget_bytes and regrown (the forward runs again) until the steps of every trajectory that
+    SUCCEEDED fit.  Returns (result, ckpt, most accepted steps)."""
+    cap = int(cfg.get("ckpt_cap") or DEFAULT_CKPT_CAP)
+    limit = _bounded_budget(cfg.get("ckpt_budget_bytes"), DEFAULT_CKPT_BUDGET, dev, 0.6)
+    row_bytes = B * capi.ckpt_record_doubles(D) * 8
+    if cap * row_bytes > limit:   # the FIRST allocation obeys the budget too (a huge batch on a small or occupied GPU)
+        cap = max(1, limit // row_bytes)
+    while True:
+        ckpt = None   # (a regrown buffer replaces the old one instead of coexisting with it)
+        ckpt = torch.empty((B, cap, capi.ckpt_record_doubles(D)), dtype=torch.float64, device=dev)
+        r = launch(ckpt)
+        # the checkpoint buffer is sized for the trajectories that SUCCEEDED: a failed one (status != 0: step budget spent,
+        # dt underflow) can have 10^5..10^6 accepted steps, contributes no gradient (its n_acc is zeroed in backward) and
+        # must not grow a [B, cap, record] buffer to hundreds of GB
+        nacc = torch.where(r["status"] == 0, r["stats"][:, 0], torch.zeros_like(r["stats"][:, 0]))
+        most = int(nacc.max().item())
+        if most <= cap:
+            return r, ckpt, most
+        cap = 1 << int(np.ceil(np.log2(most + 1)))  # the buffer was too small: run the forward again with room
+        if cap * row_bytes > limit and most * row_bytes <= limit:
+            cap = limit // row_bytes   # the power of two does not fit the budget, the steps themselves do
+        need = cap * row_bytes
+        if need > limit:
+            raise capi.IonodeError(f"checkpoints of {most} accepted steps x {B} trajectories need {need / 2**30:.1f} GiB "
+                                   f"(> ckpt_budget_bytes = {limit / 2**30:.1f} GiB): split the batch or raise the budget")
+
+
+def plan_backward_chunks(n_iter, tiles, record_floats, packet_doubles, budget, need_w, two_phase):
+    """How _Solve.backward cuts the n_iter sweep iterations into launches: (chunk, n_buf, bounds) -- iterations per chunk, buffer
+    pairs (2: the next chunk is produced while this one is reduced / walked), and the chunks' [it0, it1) ranges.  Pure arithmetic
+    (tests/test_host_logic.py replays tests/golden/grad_chunk_plans.json through it).
+      with weight gradients   a chunk's record stream (6 records of record_floats fp32 per tile and iteration) fits the budget; once
+                              that takes more than one chunk there are two buffers of half the budget each
+      two-phase without them  the packets (packet_doubles fp64 per tile and iteration) are what a chunk holds: two buffers, at most
+                              256 iterations each, which also keeps phase A one chunk ahead
+      otherwise               one launch
+    Two-phase chunks stay inside MAX_RECOMPUTE_ITERS (HIP's grid.y limit for phase A)."""
+    most = min(n_iter, MAX_RECOMPUTE_ITERS) if two_phase else n_iter
+    if need_w:
+        per_it = tiles * 6 * record_floats * 4
+        chunk = max(1, min(most, budget // per_it))
+        if chunk < n_iter:
+            chunk = max(1, min(most, (budget // 2) // per_it))
+    elif two_phase:
+        chunk = max(1, min(most, 256, (budget // 2) // (tiles * packet_doubles * 8)))
+    else:
+        chunk = n_iter
+    n_buf = 2 if chunk < n_iter and (need_w or two_phase) else 1
+    return chunk, n_buf, [(it0, min(n_iter, it0 + chunk)) for it0 in range(0, n_iter, chunk)]
+
+
+def _resolve_max_step(model, params, prot_v, v_oob, max_step):
+    """max_step of solve / sum_of_squares as a number: "auto" = stable_step_cap(); warns (at the user's call: two frames up) when
+    the rate parameters require grad and no cap is set."""
+    if isinstance(max_step, str):
+        if max_step != "auto":
+            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
+        return stable_step_cap(model, params, prot_v, v_oob)
+    if float(max_step) == 0.0 and isinstance(params, torch.Tensor) and params.requires_grad:
+        import warnings
+        warnings.warn("gradients w.r.t. the rate parameters through an UNCAPPED dopri5 solve: at equilibria dopri5 accepts steps with "
+                      "h*lambda >> 1 whose exact derivative amplifies rounding noise without bound (|dL/dp| ~ 1e36 on long holds, "
+                      "DESIGN.md 5.4).  Pass max_step='auto' (= 3 / lambda_max of the rate constants, grad.stable_step_cap) or a "
+                      "value in ms; the forward values then follow the capped step sequence.", RuntimeWarning, stacklevel=3)
+    return max_step
+
+
 def grad_image(weights_flat, L, N, dev, key=None):
     """Device-resident grad image (forward + transposed MFMA fragments) of a flat fp32 state dict."""
     ck = (key, L, N, str(dev)) if key is not None else None
@@ -124,38 +193,17 @@ class _Solve(torch.autograd.Function):
         dev = y0.device
         L, N = cfg["mlp_layers"], cfg["mlp_width"]
         B = y0.shape[0]
-        cap = int(cfg.get("ckpt_cap") or DEFAULT_CKPT_CAP)
         w_np, packed = None, None
         if weights_flat is not None:   # (None: the closed-form HH 2-state model)
             w_np = weights_flat.detach().to(torch.float32).cpu().numpy()
             from . import batched  # packed forward image: shared cache with the plain solve
             packed = batched.packed_weights(w_np, L, N, dev, key=cfg.get("weights_key"))
-        limit = _bounded_budget(cfg.get("ckpt_budget_bytes"), DEFAULT_CKPT_BUDGET, dev, 0.6)
-        row_bytes = B * (4 + 8 * y0.shape[1]) * 8
-        if cap * row_bytes > limit:   # the FIRST allocation obeys the budget too (a huge batch on a small or occupied GPU)
-            cap = max(1, limit // row_bytes)
-        while True:
-            ckpt = torch.empty((B, cap, 4 + 8 * y0.shape[1]), dtype=torch.float64, device=dev)
-            r = capi.dopri5(cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], mlp_packed=packed,
-                            mlp_layers=L, mlp_width=N, prot_t=cfg.get("prot_t"), prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"],
-                            prot_of_traj=cfg.get("prot_of_traj"), rtol=cfg["rtol"], atol=cfg["atol"], v_oob=cfg["v_oob"],
-                            max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"], max_step=cfg.get("max_step", 0.0), ckpt=ckpt,
-                            tile_waves=cfg.get("tile_waves", 0),
-                            t_eval_hint=cfg.get("t_eval_hint", "auto"))
-            # the checkpoint buffer is sized for the trajectories that SUCCEEDED: a failed one (status != 0: step budget spent,
-            # dt underflow) can have 10^5..10^6 accepted steps, contributes no gradient (its n_acc is zeroed in backward) and
-            # must not grow a [B, cap, 4 + 8 D] buffer to hundreds of GB
-            nacc = torch.where(r["status"] == 0, r["stats"][:, 0], torch.zeros_like(r["stats"][:, 0]))
-            most = int(nacc.max().item())
-            if most <= cap:
-                break
-            cap = 1 << int(np.ceil(np.log2(most + 1)))  # the buffer was too small: run the forward again with room
-            if cap * row_bytes > limit and most * row_bytes <= limit:
-                cap = limit // row_bytes   # the power of two does not fit the budget, the steps themselves do
-            need = cap * row_bytes
-            if need > limit:
-                raise capi.IonodeError(f"checkpoints of {most} accepted steps x {B} trajectories need {need / 2**30:.1f} GiB "
-                                       f"(> ckpt_budget_bytes = {limit / 2**30:.1f} GiB): split the batch or raise the budget")
+        r, ckpt, most = _forward_with_checkpoints(lambda ckpt: capi.dopri5(
+            cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], mlp_packed=packed,
+            mlp_layers=L, mlp_width=N, prot_t=cfg.get("prot_t"), prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"],
+            prot_of_traj=cfg.get("prot_of_traj"), rtol=cfg["rtol"], atol=cfg["atol"], v_oob=cfg["v_oob"],
+            max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"], max_step=cfg.get("max_step", 0.0), ckpt=ckpt,
+            tile_waves=cfg.get("tile_waves", 0), t_eval_hint=cfg.get("t_eval_hint", "auto")), B, y0.shape[1], cfg, dev)
         ctx.cfg, ctx.desc = cfg, r["desc"]
         ctx.w_np = w_np
         ctx.save_for_backward(params.detach(), ckpt, r["stats"], r["status"])
@@ -188,7 +236,6 @@ class _Solve(torch.autograd.Function):
         recf = lib.ionode_grad_record_floats(L, N) if need_w else 0
         partf = lib.ionode_grad_partial_floats(L, N) if need_w else 0
         budget = _bounded_budget(cfg.get("record_budget_bytes"), DEFAULT_RECORD_BUDGET, dev, 0.5)
-        chunk = n_iter if not need_w else max(1, min(n_iter, budget // (tiles * 6 * recf * 4)))
         acc = torch.zeros(partf, dtype=torch.float64, device=dev) if need_w else None
         main = torch.cuda.current_stream(dev)
         # Two-phase sweep (NN models; csrc/ionode_grad.hpp).  A stage's vector-Jacobian product is linear in its seed
@@ -198,23 +245,9 @@ class _Solve(torch.autograd.Function):
         # only, one wavefront per tile); the reduction of a finished chunk (ionode_grad_reduce_unit: records scaled by the seeds
         # the walk wrote) runs on a third stream.  Records and packets are double-buffered.
         two_phase = bool(cfg.get("two_phase", os.environ.get("IONODE_GRAD_ONE_PHASE", "0") != "1")) and image is not None
-        if two_phase:   # small batch, small net, very long solve: every phase-A launch stays inside HIP's grid.y limit,
-            chunk = min(chunk, MAX_RECOMPUTE_ITERS)   # decided BEFORE the chunk count and the buffering that follow from it
-        n_chunks = (n_iter + chunk - 1) // chunk
-        n_buf = 2 if (n_chunks > 1 and (need_w or two_phase)) else 1
-        if need_w and n_buf == 2:
-            chunk = max(1, min(n_iter, (budget // 2) // (tiles * 6 * recf * 4)))
-            if two_phase:
-                chunk = min(chunk, MAX_RECOMPUTE_ITERS)
-            n_chunks = (n_iter + chunk - 1) // chunk
-        elif two_phase and not need_w:
-            # no record stream: the packets are what a chunk holds (two buffers); bounded chunks also keep phase A one chunk ahead
-            per_it = tiles * int(lib.ionode_grad_packet_doubles()) * 8
-            chunk = max(1, min(n_iter, 256, (budget // 2) // per_it))
-            n_chunks = (n_iter + chunk - 1) // chunk
-            n_buf = 2 if n_chunks > 1 else 1
-        records = [torch.empty(tiles * chunk * 6 * recf, dtype=torch.float32, device=dev) for _ in range(n_buf)] if need_w else [None] * n_buf
         pkd = int(lib.ionode_grad_packet_doubles()) if two_phase else 0
+        chunk, n_buf, bounds = plan_backward_chunks(n_iter, tiles, recf, pkd, budget, need_w, two_phase)
+        records = [torch.empty(tiles * chunk * 6 * recf, dtype=torch.float32, device=dev) for _ in range(n_buf)] if need_w else [None] * n_buf
         packets = [torch.empty(tiles * chunk * pkd, dtype=torch.float64, device=dev) for _ in range(n_buf)] if two_phase else [None] * n_buf
         side = torch.cuda.Stream(dev) if (need_w and n_buf == 2) else main          # reductions
         pre = torch.cuda.Stream(dev) if (two_phase and n_buf == 2) else main         # phase A
@@ -225,7 +258,6 @@ class _Solve(torch.autograd.Function):
         desc.ckpt, desc.ckpt_cap = ckpt.data_ptr(), ckpt.shape[1]
         common = (_ptr(image), _ptr(params), _ptr(cfg["prot_v"]), _ptr(cfg.get("prot_t")), _ptr(cfg.get("prot_of_traj")),
                   _ptr(cfg["t_eval"]), _ptr(n_acc))
-        bounds = [(it0, min(n_iter, it0 + chunk)) for it0 in range(0, n_iter, chunk)]
 
         def phase_a(k):
             it0, it1 = bounds[k]
@@ -312,16 +344,7 @@ def solve(model, weights_flat, params, prot_v, y0, t_eval, *, mlp_layers=0, mlp_
     tiles, expensive tiles first -- pays from two tiles per compute unit, B > 4096); y and status are then in LAUNCH order
     (row k = trajectory order[k]), and the gradients still arrive at params / y0 in the caller's order (the gather is part of
     the autograd graph)."""
-    if isinstance(max_step, str):
-        if max_step != "auto":
-            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
-        max_step = stable_step_cap(model, params, prot_v, v_oob)
-    elif float(max_step) == 0.0 and isinstance(params, torch.Tensor) and params.requires_grad:
-        import warnings
-        warnings.warn("gradients w.r.t. the rate parameters through an UNCAPPED dopri5 solve: at equilibria dopri5 accepts steps with "
-                      "h*lambda >> 1 whose exact derivative amplifies rounding noise without bound (|dL/dp| ~ 1e36 on long holds, "
-                      "DESIGN.md 5.4).  Pass max_step='auto' (= 3 / lambda_max of the rate constants, grad.stable_step_cap) or a "
-                      "value in ms; the forward values then follow the capped step sequence.", RuntimeWarning, stacklevel=2)
+    max_step = _resolve_max_step(model, params, prot_v, v_oob, max_step)
     if model in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
         # closed-form models (train-s1.py:161-177, train-d1.py:165-187): gradients w.r.t. the rate parameters and y0; no weights
         if weights_flat is not None:
@@ -374,32 +397,13 @@ class _SumOfSquares(torch.autograd.Function):
     def forward(ctx, params, y0, cfg):
         dev = y0.device
         B, D = y0.shape
-        cap = int(cfg.get("ckpt_cap") or DEFAULT_CKPT_CAP)
-        # checkpoint sizing, regrowth and budget: the rules of _Solve.forward
-        limit = _bounded_budget(cfg.get("ckpt_budget_bytes"), DEFAULT_CKPT_BUDGET, dev, 0.6)
-        row_bytes = B * (4 + 8 * D) * 8
-        if cap * row_bytes > limit:
-            cap = max(1, limit // row_bytes)
-        while True:
-            ckpt = None   # (a regrown buffer replaces the old one instead of coexisting with it)
-            ckpt = torch.empty((B, cap, 4 + 8 * D), dtype=torch.float64, device=dev)
-            r = capi.dopri5(cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], prot_t=cfg["prot_t"],
-                            prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"], prot_of_traj=cfg["prot_of_traj"], rtol=cfg["rtol"],
-                            atol=cfg["atol"], v_oob=cfg["v_oob"], max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"],
-                            max_step=cfg["max_step"], ckpt=ckpt, obs_g=cfg["obs_g"], obs_e=cfg["obs_e"],
-                            obs_open_state_only=cfg["obs_open_state_only"], t_eval_hint=cfg["t_eval_hint"],
-                            sse_ref=cfg["sse_ref"], states=False)
-            nacc = torch.where(r["status"] == 0, r["stats"][:, 0], torch.zeros_like(r["stats"][:, 0]))
-            most = int(nacc.max().item())
-            if most <= cap:
-                break
-            cap = 1 << int(np.ceil(np.log2(most + 1)))
-            if cap * row_bytes > limit and most * row_bytes <= limit:
-                cap = limit // row_bytes
-            need = cap * row_bytes
-            if need > limit:
-                raise capi.IonodeError(f"checkpoints of {most} accepted steps x {B} trajectories need {need / 2**30:.1f} GiB "
-                                       f"(> ckpt_budget_bytes = {limit / 2**30:.1f} GiB): split the batch or raise the budget")
+        r, ckpt, _most = _forward_with_checkpoints(lambda ckpt: capi.dopri5(
+            cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], prot_t=cfg["prot_t"],
+            prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"], prot_of_traj=cfg["prot_of_traj"], rtol=cfg["rtol"],
+            atol=cfg["atol"], v_oob=cfg["v_oob"], max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"],
+            max_step=cfg["max_step"], ckpt=ckpt, obs_g=cfg["obs_g"], obs_e=cfg["obs_e"],
+            obs_open_state_only=cfg["obs_open_state_only"], t_eval_hint=cfg["t_eval_hint"],
+            sse_ref=cfg["sse_ref"], states=False), B, D, cfg, dev)
         ctx.cfg, ctx.desc = cfg, r["desc"]
         ctx.vtab = r["v_at_outputs"]   # the descriptor points at it: the backward reads V(t_k) from the same table
         ctx.sdt = y0.dtype
@@ -468,16 +472,7 @@ def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, p
     if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
         raise capi.IonodeError("grad.sum_of_squares: the fused objective gradient is built for the closed-form HH 2-state and 6-state "
                                "models; for NN models use grad.solve and form the sum of squares in torch")
-    if isinstance(max_step, str):
-        if max_step != "auto":
-            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
-        max_step = stable_step_cap(model, params, prot_v, v_oob)
-    elif float(max_step) == 0.0 and isinstance(params, torch.Tensor) and params.requires_grad:
-        import warnings
-        warnings.warn("gradients w.r.t. the rate parameters through an UNCAPPED dopri5 solve: at equilibria dopri5 accepts steps with "
-                      "h*lambda >> 1 whose exact derivative amplifies rounding noise without bound (|dL/dp| ~ 1e36 on long holds, "
-                      "DESIGN.md 5.4).  Pass max_step='auto' (= 3 / lambda_max of the rate constants, grad.stable_step_cap) or a "
-                      "value in ms; the forward values then follow the capped step sequence.", RuntimeWarning, stacklevel=2)
+    max_step = _resolve_max_step(model, params, prot_v, v_oob, max_step)
     if not (isinstance(y0, torch.Tensor) and y0.is_cuda):
         raise capi.IonodeError("no HIP tensors: the integrator and its backward sweep have no CPU path")
     D = 6 if model == capi.MODEL_MARKOV6 else 2

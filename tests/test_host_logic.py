@@ -479,3 +479,32 @@ def test_dispatch_table_and_images_are_pinned(ion):
     assert [tuple(p[:2]) for p in doc["packs"]] == list(gen.PACK_SHAPES)
     for L, N, floats, sha in doc["packs"]:
         assert gen.pack_digest(ion.capi, L, N) == (floats, sha), (L, N)
+
+
+def test_backward_chunk_plans_are_pinned(ion):
+    """tests/golden/grad_chunk_plans.json (tests/golden/make_grad_chunk_plans.py): chunk size, buffer count and chunk bounds of the
+    backward sweep for every need_w x two_phase combination, n_iter around 1, 256 and phase A's grid.y limit, 1 and 4096 tiles, and
+    budgets that hold the whole sweep, half of it, one iteration and less than one -- recorded from the arithmetic _Solve.backward
+    carried inline before grad.plan_backward_chunks, with a tag per branch that arithmetic took; every branch occurs."""
+    import importlib.util
+    import json
+    golden = os.path.join(os.path.dirname(__file__), "golden")
+    spec = importlib.util.spec_from_file_location("make_grad_chunk_plans", os.path.join(golden, "make_grad_chunk_plans.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    doc = json.load(open(os.path.join(golden, "grad_chunk_plans.json")))
+    assert doc["columns"] == list(gen.COLUMNS) and doc["packet_doubles"] == gen.PACKET_DOUBLES
+    ins = [r["in"] for r in doc["rows"]]
+    assert {(r[0], r[1]) for r in ins} == {(a, b) for a in (False, True) for b in (False, True)}
+    assert {r[2] for r in ins} >= {1, 2, 255, 256, 257, 65535 * 4 - 1, 65535 * 4, 65535 * 4 + 1} and {r[3] for r in ins} == {1, 4096}
+    # the four budget cases (whole sweep fits, exactly two chunks, one iteration per chunk, too small for one) at every grid point
+    assert set(gen.BUDGETS) == {"fits", "two_chunks", "one_iteration", "too_small"} and {tuple(r) for r in ins} == set(gen.rows())
+    assert {t for r in doc["rows"] for t in r["tags"]} == set(gen.BRANCHES) == set(doc["branches"])
+    clamped = 0
+    for r in doc["rows"]:
+        need_w, two_phase, n_iter, tiles, recf, budget = r["in"]
+        chunk, n_buf, bounds = ion.grad.plan_backward_chunks(n_iter, tiles, recf, doc["packet_doubles"], budget, need_w, two_phase)
+        assert gen.digest(chunk, n_buf, bounds) == r["plan"], r["in"]
+        clamped += chunk == 1 and n_iter > 1 and (need_w or two_phase)
+    assert clamped >= 8   # budgets too small for a single iteration: chunk clamps to 1
+    assert ion.grad.MAX_RECOMPUTE_ITERS == gen.MAX_RECOMPUTE_ITERS
