@@ -266,6 +266,34 @@ int ionode_dopri5_backward_sweep(const ionode_desc *d, int32_t it_begin, int32_t
 int ionode_grad_reduce_unit(int32_t mlp_layers, int32_t mlp_width, const float *records, int64_t n_records, int32_t n_slabs,
                             float *partials, void *stream);
 
+/*
+ * Fused sum-of-squares gradient for NN-f / NN-d on the two-phase sweep (since ABI 10, added later: new symbols only, ionode_desc and
+ * every earlier entry point unchanged).  The objective and the forward are ionode_dopri5_backward_sse's (d->ckpt and d->sse_out set,
+ * y_out = i_out = NULL allowed); the upstream gradient is grad_sse[b] = dL/dsse[b].  Output gradients enter the two-phase sweep in one
+ * place -- the G_c sums of a step's packet -- and in the sample-0 term of dL/dy0; both depend on the step's checkpoint, the protocol,
+ * sse_ref and grad_sse only:
+ *   ionode_dopri5_backward_sse_gc()         one wavefront per (trajectory, iteration) of the chunk: re-evaluates the step's output samples
+ *       from its checkpoint and writes G_c into `packets` (the chunk's buffer, as for _recompute; zeros where a trajectory has no step);
+ *       the launch with it_end == n_iter also writes sse_grad_y0 [B][2] fp64, the sample-0 term 2 grad_sse[b] r_0 dr_0/dy0;
+ *   ionode_dopri5_backward_recompute_sse()  ionode_dopri5_backward_recompute without grad_y: leaves the packets' G_c alone;
+ *   ionode_dopri5_backward_sweep_sse()      ionode_dopri5_backward_sweep with sse_grad_y0 in the place of grad_y.
+ * Per chunk: sse_gc and recompute_sse (either order, the same `packets`), then sweep_sse, then ionode_grad_reduce_unit.  Neither y
+ * nor dL/dy is ever materialised.  All three read sse_ref, ckpt, ckpt_cap (sse_gc also obs_g, obs_e, obs_open_state_only and the
+ * optional v_at_outputs) from the descriptor.  IONODE_ERR_ARG for a missing buffer (sse_ref, ckpt, grad_sse, packets, sse_grad_y0,
+ * ...) or a bad iteration range; IONODE_ERR_UNSUPPORTED for traj_per_image > 0, for the closed-form models (ionode_dopri5_backward_sse
+ * serves those) and for widths or depths the sweep does not serve.
+ */
+int ionode_dopri5_backward_sse_gc(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *prot_v,
+                                  const double *prot_t, const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
+                                  const double *grad_sse, double *packets, double *sse_grad_y0, void *stream);
+int ionode_dopri5_backward_recompute_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
+                                         const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
+                                         const double *t_eval, const int32_t *n_accepted, float *records, double *packets, void *stream);
+int ionode_dopri5_backward_sweep_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
+                                     const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
+                                     const double *t_eval, const int32_t *n_accepted, const double *sse_grad_y0, double *state,
+                                     float *records, const double *packets, double *grad_params, double *grad_y0, void *stream);
+
 /* floats of one slab's partial gradient: [NP][4]{db0, dW0[.][0], dW0[.][1], 0} | L x (dW_l [NP][NP] + db_l [NP]) | dwl [NP] +
  * {dbl, 0, 0, 0}, NP = 16 * ceil(N / 16), rows/columns >= N are padding */
 size_t ionode_grad_partial_floats(int32_t mlp_layers, int32_t mlp_width);

@@ -28,6 +28,7 @@ EXPORTS = (
     "ionode_launch_geometry", "ionode_kernel_name", "ionode_last_kernel_name", "ionode_lane_wise_from", "ionode_dopri5", "ionode_protocol_at_outputs",
     "ionode_grad_image_floats", "ionode_grad_pack", "ionode_grad_record_floats", "ionode_dopri5_backward", "ionode_dopri5_backward_sse",
     "ionode_grad_packet_doubles", "ionode_dopri5_backward_recompute", "ionode_dopri5_backward_sweep",
+    "ionode_dopri5_backward_sse_gc", "ionode_dopri5_backward_recompute_sse", "ionode_dopri5_backward_sweep_sse",
     "ionode_grad_partial_floats", "ionode_grad_reduce", "ionode_grad_reduce_unit", "ionode_grad_reduce_slabs", "ionode_grad_last_error",
     "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh",
 )
@@ -105,6 +106,13 @@ def lib():
         L.ionode_dopri5_backward_recompute.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11
         L.ionode_dopri5_backward_sweep.restype = C.c_int
         L.ionode_dopri5_backward_sweep.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 14
+        # the fused sum-of-squares objective on the two-phase sweep (NN-f / NN-d)
+        L.ionode_dopri5_backward_sse_gc.restype = C.c_int
+        L.ionode_dopri5_backward_sse_gc.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9
+        L.ionode_dopri5_backward_recompute_sse.restype = C.c_int
+        L.ionode_dopri5_backward_recompute_sse.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10
+        L.ionode_dopri5_backward_sweep_sse.restype = C.c_int
+        L.ionode_dopri5_backward_sweep_sse.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 14
         L.ionode_grad_reduce.restype = C.c_int
         L.ionode_grad_reduce.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.ionode_grad_reduce_slabs.restype = C.c_int32

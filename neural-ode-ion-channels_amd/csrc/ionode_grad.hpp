@@ -601,6 +601,8 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
 
     // ---- adjoints of the interpolant coefficients: G_c = sum_k gy[k] * x_k^c over the step's output samples ----
     // (a copy of ionode_grad_sweep_body.hpp's reduction: a shared routine compiled to other code -- DESIGN_HISTORY.md, "The backward sweep's step algebra"; correct both)
+    // grad_y == NULL (wave-uniform): the fused objective -- ionode_grad_sse_gc_kernel (ionode_grad_gc.hpp) writes the packets' G_c, nothing is reduced here
+    if (a.grad_y != nullptr) {
     // (the first 64 samples of the wavefront's four trajectories: all loads in flight before the first is used)
     double tk0[4] = {0.0, 0.0, 0.0, 0.0};
     S gy0[4][D] = {};
@@ -659,13 +661,16 @@ __global__ void __launch_bounds__(256, (NT <= 13 ? IONODE_RECOMPUTE_WG_PER_CU : 
           for (int d = 0; d < D; ++d) Gs[jj * (5 * D) + c * D + d] = P[c][d];
       }
     }
+    }
     __syncthreads();
     if (pk_writer) {
       pk[pkt::DTS] = dts; pk[pkt::STEP] = step ? 1.0 : 0.0; pk[pkt::INITEV] = initev ? 1.0 : 0.0; pk[3] = 0.0;
+      if (a.grad_y != nullptr) {
 #pragma unroll
-      for (int c = 0; c < 5; ++c)
+        for (int c = 0; c < 5; ++c)
 #pragma unroll
-        for (int d = 0; d < D; ++d) pk[pkt::GC + c * D + d] = Gs[j * (5 * D) + c * D + d];
+          for (int d = 0; d < D; ++d) pk[pkt::GC + c * D + d] = Gs[j * (5 * D) + c * D + d];
+      }
     }
     // ---- the six stages' scalar work, AHEAD of their products (round 5): stage voltages (pure functions of (t0, dt): the five distinct
     // lookups in flight together -- stage i = 5 shares i = 4's time), stage inputs Y_i, rate exponentials, the packet; what a product needs
@@ -850,7 +855,7 @@ __global__ void __launch_bounds__(64) ionode_grad_walk_kernel(const GArgs a) {
 #pragma unroll
       for (int i = 0; i < NPAR; ++i) a.grad_params[(size_t)traj * NPAR + i] = gp[i];
 #pragma unroll
-      for (int d = 0; d < D; ++d) a.grad_y0[(size_t)traj * D + d] = lam[d] + (double)gy[d];  // solution[0] = y0
+      for (int d = 0; d < D; ++d) a.grad_y0[(size_t)traj * D + d] = lam[d] + (a.grad_y != nullptr ? (double)gy[d] : a.sse_y0[(size_t)traj * D + d]);  // solution[0] = y0 (fused objective: its sample-0 term)
     }
   }
 }

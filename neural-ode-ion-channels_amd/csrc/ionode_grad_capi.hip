@@ -20,6 +20,7 @@ using ionode::SweepFn;
 // launchers that have no width: the closed-form models' sweeps (NT = 1, unused) and the NN models' walk
 template <int MODEL> SweepFn closed_sweep(int f32) { return f32 ? &ionode::launch_sweep<MODEL, float, 1> : &ionode::launch_sweep<MODEL, double, 1>; }
 template <int MODEL> SweepFn closed_sweep_sse(int f32) { return f32 ? &ionode::launch_sweep_sse<MODEL, float> : &ionode::launch_sweep_sse<MODEL, double>; }
+inline SweepFn sse_gc(int f32) { return f32 ? &ionode::launch_sse_gc<float> : &ionode::launch_sse_gc<double>; }
 template <int MODEL> SweepFn walk(int f32) { return f32 ? &ionode::launch_walk<MODEL, float> : &ionode::launch_walk<MODEL, double>; }
 
 // nullptr: no variant of that width (a width without a sweep has no walk either, though the walk kernel itself has no width)
@@ -124,7 +125,9 @@ int ionode_grad_pack(const float *w, int32_t L, int32_t N, float *out) {
 static int backward_impl(Sweep which, const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
                          const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                          const double *t_eval, const int32_t *n_accepted, const void *grad_y, double *state,
-                         float *records, double *packets, double *grad_params, double *grad_y0, void *stream) {
+                         float *records, double *packets, double *grad_params, double *grad_y0, void *stream,
+                         bool fused = false, const double *sse_y0 = nullptr) {
+  // fused (two-phase only): the sum-of-squares objective -- no grad_y; the walk reads the sample-0 term of dL/dy0 from sse_y0
   if (!d) { gerr("null descriptor"); return IONODE_ERR_ARG; }
   const bool two_phase = which != Sweep::OnePhase;
   if (two_phase && (!packets || (d->model != IONODE_MODEL_NNF && d->model != IONODE_MODEL_NND))) {
@@ -135,7 +138,7 @@ static int backward_impl(Sweep which, const ionode_desc *d, int32_t it_begin, in
   if (d->model < 0 || d->model > 3) { gerr("backward sweep: unknown model"); return IONODE_ERR_UNSUPPORTED; }
   if (!desc_consistent(d)) { gerr("inconsistent descriptor"); return IONODE_ERR_ARG; }
   const bool adjoint = which != Sweep::Recompute;   // the launch reads and writes the adjoint state
-  if ((!grad_image && !closed) || !params || !prot_v || !t_eval || !n_accepted || !grad_y || (adjoint && (!state || !grad_params || !grad_y0)) || !d->ckpt || d->ckpt_cap < 1) {
+  if ((!grad_image && !closed) || !params || !prot_v || !t_eval || !n_accepted || (fused ? (which == Sweep::Walk && !sse_y0) : !grad_y) || (adjoint && (!state || !grad_params || !grad_y0)) || !d->ckpt || d->ckpt_cap < 1) {
     gerr("ionode_dopri5_backward: required buffer is NULL (ckpt / ckpt_cap come from the descriptor)"); return IONODE_ERR_ARG;
   }
   if (bad_range(it_begin, it_end, n_iter)) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
@@ -154,7 +157,7 @@ static int backward_impl(Sweep which, const ionode_desc *d, int32_t it_begin, in
     return IONODE_ERR_UNSUPPORTED;
   }
   GArgs a = fill_args(d, L, NP, it_begin, it_end, n_iter, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, state, grad_params, grad_y0);
-  a.k.N = d->mlp_width; a.img = grad_image; a.grad_y = grad_y;
+  a.k.N = d->mlp_width; a.img = grad_image; a.grad_y = fused ? nullptr : grad_y; a.sse_y0 = const_cast<double *>(sse_y0);
   a.records = closed ? nullptr : records;
   a.record_floats = ionode::grad_record_floats(L, NT);
   a.packets = two_phase ? packets : nullptr;
@@ -208,6 +211,68 @@ int ionode_dopri5_backward_sweep(const ionode_desc *d, int32_t it_begin, int32_t
                                  void *stream) {
   return backward_impl(Sweep::Walk, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
                        state, records, const_cast<double *>(packets), grad_params, grad_y0, stream);
+}
+
+// ---- the fused sum-of-squares objective on the two-phase sweep (NN-f / NN-d) ----
+// what the three entry points check first, in ionode_dopri5_backward_sse's order; nothing is launched before it passes
+static int sse_nn_check(const char *who, const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter) {
+  char m[200];
+  if (!d) { gerr("null descriptor"); return IONODE_ERR_ARG; }
+  if (d->model != IONODE_MODEL_NNF && d->model != IONODE_MODEL_NND) {
+    snprintf(m, sizeof m, "%s: NN-f / NN-d only (closed-form models: ionode_dopri5_backward_sse)", who); gerr(m); return IONODE_ERR_UNSUPPORTED;
+  }
+  if (d->traj_per_image > 0) { snprintf(m, sizeof m, "%s: traj_per_image must be 0", who); gerr(m); return IONODE_ERR_UNSUPPORTED; }
+  if (!desc_consistent(d)) { gerr("inconsistent descriptor"); return IONODE_ERR_ARG; }
+  if (!d->sse_ref || !d->ckpt || d->ckpt_cap < 1) {
+    snprintf(m, sizeof m, "%s: required buffer is NULL (sse_ref / ckpt / ckpt_cap come from the descriptor)", who); gerr(m); return IONODE_ERR_ARG;
+  }
+  if (bad_range(it_begin, it_end, n_iter)) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
+  if (d->mlp_layers < 1 || d->mlp_width < 1) { gerr("bad MLP shape"); return IONODE_ERR_ARG; }
+  const int NT = np_of(d->mlp_width) / 16;
+  if (!find_sweep(Sweep::Walk, d->model, d->state_f32 ? 1 : 0, NT) || d->mlp_layers > 15 ||
+      ionode::grad_lds_bytes(d->mlp_layers, NT) + 16 + ionode::grad_walk_lds_bytes() > 160 * 1024) {
+    gerr("backward sweep: (L, N) outside the compiled variants (N pads to 16, 112, 208 or 512; at most 15 hidden layers)");
+    return IONODE_ERR_UNSUPPORTED;
+  }
+  return IONODE_OK;
+}
+
+int ionode_dopri5_backward_sse_gc(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *prot_v,
+                                  const double *prot_t, const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
+                                  const double *grad_sse, double *packets, double *sse_grad_y0, void *stream) {
+  const int rc = sse_nn_check("ionode_dopri5_backward_sse_gc", d, it_begin, it_end, n_iter);
+  if (rc != IONODE_OK) return rc;
+  if (!grad_sse || !prot_v || !t_eval || !n_accepted || !packets || !sse_grad_y0) {
+    gerr("ionode_dopri5_backward_sse_gc: required buffer is NULL"); return IONODE_ERR_ARG;
+  }
+  if ((int64_t)it_end - it_begin > (int64_t)65535 * ionode::GRAD_GC_WAVES) {
+    gerr("ionode_dopri5_backward_sse_gc: at most 65535 x 4 iterations per launch (HIP's grid.y limit): split the range"); return IONODE_ERR_ARG;
+  }
+  GArgs a = fill_args(d, d->mlp_layers, np_of(d->mlp_width), it_begin, it_end, n_iter, nullptr, prot_v, prot_t, prot_of_traj, t_eval, n_accepted,
+                      nullptr, nullptr, nullptr);
+  a.packets = packets; a.sse_y0 = sse_grad_y0;
+  a.grad_sse = grad_sse; a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
+  a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
+  return launch(sse_gc(d->state_f32), a, 0, stream);
+}
+
+int ionode_dopri5_backward_recompute_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
+                                         const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
+                                         const double *t_eval, const int32_t *n_accepted, float *records, double *packets, void *stream) {
+  const int rc = sse_nn_check("ionode_dopri5_backward_recompute_sse", d, it_begin, it_end, n_iter);
+  if (rc != IONODE_OK) return rc;
+  return backward_impl(Sweep::Recompute, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, nullptr,
+                       nullptr, records, packets, nullptr, nullptr, stream, true, nullptr);
+}
+
+int ionode_dopri5_backward_sweep_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
+                                     const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
+                                     const double *t_eval, const int32_t *n_accepted, const double *sse_grad_y0, double *state,
+                                     float *records, const double *packets, double *grad_params, double *grad_y0, void *stream) {
+  const int rc = sse_nn_check("ionode_dopri5_backward_sweep_sse", d, it_begin, it_end, n_iter);
+  if (rc != IONODE_OK) return rc;
+  return backward_impl(Sweep::Walk, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, nullptr,
+                       state, records, const_cast<double *>(packets), grad_params, grad_y0, stream, true, sse_grad_y0);
 }
 
 static int reduce_impl(int32_t L, int32_t N, const float *records, int64_t n_records, int32_t n_slabs, float *partials, void *stream,

@@ -2,6 +2,7 @@
 // (ionode_grad_capi.hip: N = 10 / 100 / 200; inst_grad32.hip: N = 500).
 #pragma once
 #include "ionode_grad.hpp"
+#include "ionode_grad_gc.hpp"
 #include "ionode_regress.hpp"
 
 namespace ionode {
@@ -32,6 +33,13 @@ void launch_walk(const GArgs &a, unsigned grid, size_t, hipStream_t s) {
 template <int MODEL, typename S>
 void launch_sweep_sse(const GArgs &a, unsigned grid, size_t lds, hipStream_t s) {
   hipLaunchKernelGGL((ionode_dopri5_backward_sse_kernel<MODEL, S>), dim3(grid), dim3(256), lds, s, a);
+}
+// G_c and the sample-0 term of the fused objective for the two-phase sweep (NN-f / NN-d): one wavefront per (trajectory, iteration);
+// grid.y = ceil(iterations / 4) <= 65535 for every chunk the recompute kernel accepts.  `grid` (tiles) and `lds` are unused.
+template <typename S>
+void launch_sse_gc(const GArgs &a, unsigned, size_t, hipStream_t s) {
+  const unsigned nb = (unsigned)((a.it_end - a.it_begin + GRAD_GC_WAVES - 1) / GRAD_GC_WAVES);
+  hipLaunchKernelGGL((ionode_grad_sse_gc_kernel<S>), dim3((unsigned)a.k.B, nb), dim3(64 * GRAD_GC_WAVES), 0, s, a);
 }
 
 using SweepFn = void (*)(const GArgs &, unsigned grid, size_t lds, hipStream_t);

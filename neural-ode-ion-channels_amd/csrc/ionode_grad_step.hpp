@@ -1,5 +1,6 @@
 // ionode_grad_step.hpp -- what the backward sweep's kernels and their host share (ionode_grad.hpp: the one-phase sweep and its
-// fused sum-of-squares variant in ionode_grad_sweep_body.hpp, the two-phase recompute and walk kernels; ionode_grad_reduce.hpp):
+// fused sum-of-squares variant in ionode_grad_sweep_body.hpp, the two-phase recompute and walk kernels; ionode_grad_gc.hpp: the fused
+// objective's G_c kernel for the two-phase sweep; ionode_grad_reduce.hpp):
 // the argument block and the layouts of the streams between the launches, each named once.  The algebra of a step is still
 // written per kernel: shared routines compiled to other code (DESIGN_HISTORY.md, "the backward sweep's step algebra").
 #pragma once
@@ -13,7 +14,7 @@ struct GArgs {
   const float *img;        // grad image (ionode_grad_pack)
   const double *ckpt;      // [B][ckpt_cap][CkptRecord<D>::WIDTH] accepted-step records of the forward launch
   const int32_t *nacc;     // [B] accepted steps to replay (0: nothing to differentiate, e.g. a failed trajectory)
-  const void *grad_y;      // [B][Nt][D] dL/dy_out in the state dtype
+  const void *grad_y;      // [B][Nt][D] dL/dy_out in the state dtype; two-phase kernels: NULL = the fused objective (G_c and the sample-0 term come from ionode_grad_sse_gc_kernel)
   double *state;           // [B][2 * D + NPAR] adjoint state carried between chunk launches: lam[D], mu[D], gp[NPAR]
   float *records;          // [n_tiles][it_end - it_begin][6][record_floats] (d, h) stream for ionode_grad_reduce, or NULL
   double *grad_params;     // [B][NPAR]   written by the launch with it_end == n_iter
@@ -29,6 +30,7 @@ struct GArgs {
   const double *v_tab;        // optional [P][Nt] V(t_k) (ionode_protocol_at_outputs), or NULL: protocol_v per sample
   double obs_g, obs_e;
   int32_t obs_open;
+  double *sse_y0;             // two-phase fused objective: [B][D] sample-0 term of dL/dy0 (ionode_grad_sse_gc_kernel writes it, the walk adds it where grad_y is NULL)
 };
 
 // ---- packet of one trajectory and step (two-phase sweep, fp64): what the recompute kernel hands to the walk ----

@@ -17,6 +17,10 @@ Three launches per backward (csrc/ionode_grad.hpp, ionode_grad_reduce.hpp), all 
             algebra only); closed-form models and two_phase=False: ionode_dopri5_backward (everything inside the walk)
   reduce    ionode_grad_reduce[_unit]: split-K fp32 MFMA GEMM of the records into per-slab partial weight gradients, summed
             here in fp64.
+sum_of_squares: the fused objective sse[b] = sum_k (i_k - ref_k)^2 with its gradient, nothing of size [B, Nt] allocated.  Closed-form
+models: the one-phase sweep with the seed formed in the kernel (ionode_dopri5_backward_sse).  NN models: the two-phase sweep above
+without grad_y -- ionode_dopri5_backward_sse_gc (csrc/ionode_grad_gc.hpp) forms each chunk's interpolant-coefficient adjoints and the
+sample-0 term, ionode_dopri5_backward_recompute_sse / _sweep_sse are the recompute and walk launches that take them.
 There is no CPU fallback: without libionode.so or a HIP device every call raises.
 """
 import ctypes as C
@@ -215,110 +219,133 @@ class _Solve(torch.autograd.Function):
     def backward(ctx, gy, _gstatus):
         cfg, desc = ctx.cfg, ctx.desc
         params, ckpt, stats, status = ctx.saved_tensors
-        dev = params.device
         L, N = cfg["mlp_layers"], cfg["mlp_width"]
-        B, Nt = desc.n_traj, desc.n_out
         need_w = ctx.needs_input_grad[0] and ctx.w_np is not None
-        lib = capi.lib()
         sdt = torch.float32 if desc.state_f32 else torch.float64
         # failed trajectories (status != 0): their rows of y are NaN-filled and carry no gradient -- zero upstream rows (a caller's
         # unmasked loss would otherwise feed NaN into the sweep) and, below, zero dL/dy0 / dL/dp rows
         failed = status != 0
         gy = torch.where(failed[:, None, None], torch.zeros((), dtype=gy.dtype, device=gy.device), gy).to(sdt).contiguous()
         n_acc = torch.where(status == 0, stats[:, 0], torch.zeros_like(stats[:, 0])).to(torch.int32).contiguous()
-        n_iter = int(n_acc.max().item()) + 1
-        image = grad_image(ctx.w_np, L, N, dev, key=cfg.get("weights_key")) if ctx.w_np is not None else None
-        D, npar = desc.n_state, (12 if desc.model == capi.MODEL_MARKOV6 else 8)
-        state = torch.empty((B, 2 * D + npar), dtype=torch.float64, device=dev)
-        g_params = torch.zeros((B, npar), dtype=torch.float64, device=dev)
-        g_y0 = torch.zeros((B, D), dtype=torch.float64, device=dev)
-        tiles = (B + 15) // 16
-        recf = lib.ionode_grad_record_floats(L, N) if need_w else 0
-        partf = lib.ionode_grad_partial_floats(L, N) if need_w else 0
-        budget = _bounded_budget(cfg.get("record_budget_bytes"), DEFAULT_RECORD_BUDGET, dev, 0.5)
-        acc = torch.zeros(partf, dtype=torch.float64, device=dev) if need_w else None
-        main = torch.cuda.current_stream(dev)
-        # Two-phase sweep (NN models; csrc/ionode_grad.hpp).  A stage's vector-Jacobian product is linear in its seed
-        # (a scalar per trajectory) and everything else it needs comes from the step's checkpoint: phase A
-        # (ionode_dopri5_backward_recompute) computes the UNIT-SEED products of every (tile, step) of a chunk at once on the whole
-        # chip, on its own stream, one chunk AHEAD of phase B (ionode_dopri5_backward_sweep: the sequential walk, adjoint algebra
-        # only, one wavefront per tile); the reduction of a finished chunk (ionode_grad_reduce_unit: records scaled by the seeds
-        # the walk wrote) runs on a third stream.  Records and packets are double-buffered.
-        two_phase = bool(cfg.get("two_phase", os.environ.get("IONODE_GRAD_ONE_PHASE", "0") != "1")) and image is not None
-        pkd = int(lib.ionode_grad_packet_doubles()) if two_phase else 0
-        chunk, n_buf, bounds = plan_backward_chunks(n_iter, tiles, recf, pkd, budget, need_w, two_phase)
-        records = [torch.empty(tiles * chunk * 6 * recf, dtype=torch.float32, device=dev) for _ in range(n_buf)] if need_w else [None] * n_buf
-        packets = [torch.empty(tiles * chunk * pkd, dtype=torch.float64, device=dev) for _ in range(n_buf)] if two_phase else [None] * n_buf
-        side = torch.cuda.Stream(dev) if (need_w and n_buf == 2) else main          # reductions
-        pre = torch.cuda.Stream(dev) if (two_phase and n_buf == 2) else main         # phase A
-        if pre is not main:
-            pre.wait_stream(main)    # gy / state / inputs were produced on the caller's stream
-        free = [None] * n_buf   # event: the reduce (or, without weight gradients, the walk) that last used this buffer pair has finished
-        ready = [None] * n_buf  # event: phase A has filled this buffer pair
-        desc.ckpt, desc.ckpt_cap = ckpt.data_ptr(), ckpt.shape[1]
-        common = (_ptr(image), _ptr(params), _ptr(cfg["prot_v"]), _ptr(cfg.get("prot_t")), _ptr(cfg.get("prot_of_traj")),
-                  _ptr(cfg["t_eval"]), _ptr(n_acc))
-
-        def phase_a(k):
-            it0, it1 = bounds[k]
-            b = k % n_buf
-            if free[b] is not None:
-                pre.wait_event(free[b])
-            rc = lib.ionode_dopri5_backward_recompute(C.byref(desc), it0, it1, n_iter, *common, _ptr(gy), _ptr(records[b]),
-                                                      _ptr(packets[b]), C.c_void_p(pre.cuda_stream))
-            if rc != 0:
-                raise capi.IonodeError(f"ionode_dopri5_backward_recompute failed ({rc}): {lib.ionode_grad_last_error().decode()}")
-            ev = torch.cuda.Event()
-            ev.record(pre)
-            ready[b] = ev
-
-        if two_phase:
-            phase_a(0)
-        for k, (it0, it1) in enumerate(bounds):
-            b = k % n_buf
-            rec = records[b]
-            if two_phase:
-                if k + 1 < len(bounds) and n_buf == 2:
-                    phase_a(k + 1)                      # one chunk ahead, beside this chunk's walk
-                main.wait_event(ready[b])
-                rc = lib.ionode_dopri5_backward_sweep(C.byref(desc), it0, it1, n_iter, *common, _ptr(gy), _ptr(state), _ptr(rec),
-                                                      _ptr(packets[b]), _ptr(g_params), _ptr(g_y0),
-                                                      C.c_void_p(main.cuda_stream))
-            else:
-                if free[b] is not None:
-                    main.wait_event(free[b])
-                rc = lib.ionode_dopri5_backward(C.byref(desc), it0, it1, n_iter, *common, _ptr(gy), _ptr(state), _ptr(rec),
-                                                _ptr(g_params), _ptr(g_y0), C.c_void_p(main.cuda_stream))
-            if rc != 0:
-                raise capi.IonodeError(f"backward sweep failed ({rc}): {lib.ionode_grad_last_error().decode()}")
-            swept = torch.cuda.Event()
-            swept.record(main)
-            if need_w:
-                n_rec = tiles * (it1 - it0) * 6
-                n_slabs = int(os.environ.get("IONODE_GRAD_SLABS", 0)) or int(lib.ionode_grad_reduce_slabs(L, N, n_rec))   # one round of workgroups on this device (env: dev override for A/B runs)
-                side.wait_event(swept)
-                with torch.cuda.stream(side):
-                    partials = torch.empty((n_slabs, partf), dtype=torch.float32, device=dev)
-                    reduce = lib.ionode_grad_reduce_unit if two_phase else lib.ionode_grad_reduce   # unit-seed records: scaled while staged
-                    rc = reduce(L, N, _ptr(rec), n_rec, n_slabs, _ptr(partials), C.c_void_p(side.cuda_stream))
-                    if rc != 0:
-                        raise capi.IonodeError(f"ionode_grad_reduce failed ({rc}): {lib.ionode_grad_last_error().decode()}")
-                    acc += partials.double().sum(0)
-                    done = torch.cuda.Event()
-                    done.record(side)
-                free[b] = done
-            else:
-                free[b] = swept
-            if two_phase and n_buf == 1 and k + 1 < len(bounds):
-                phase_a(k + 1)                          # single buffer: strictly alternate
-        if need_w and side is not main:
-            main.wait_stream(side)
-        if pre is not main:
-            main.wait_stream(pre)
+        acc, g_params, g_y0 = _sweep(cfg, desc, ctx.w_np, need_w, params, ckpt, n_acc, gy=gy)
         g_params[failed] = 0.0
         g_y0[failed] = 0.0
         g_w = unpack_partial(acc, L, N).to(torch.float32) if need_w else None
         return g_w, (g_params if ctx.needs_input_grad[1] else None), (g_y0.to(sdt) if ctx.needs_input_grad[2] else None), None
+
+
+def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, gy=None, g_sse=None):
+    """The backward sweep's chunk loop, shared by _Solve.backward (gy [B, Nt, D]: the upstream dL/dy in the state dtype) and
+    _SumOfSquaresNN.backward (g_sse [B] fp64: the upstream dL/dsse of the fused objective, NN models, two-phase only -- per chunk
+    ionode_dopri5_backward_sse_gc forms the packets' G_c on the phase-A stream and the products run without grad_y).  n_acc [B]
+    int32: accepted steps to replay (0 for failed trajectories).  Returns (padded partial weight gradient fp64 | None, dL/dp
+    [B, NPAR], dL/dy0 [B, D]), the rows of failed trajectories not yet zeroed."""
+    dev = params.device
+    L, N = cfg["mlp_layers"], cfg["mlp_width"]
+    B = desc.n_traj
+    lib = capi.lib()
+    fused = g_sse is not None
+    n_iter = int(n_acc.max().item()) + 1
+    image = grad_image(w_np, L, N, dev, key=cfg.get("weights_key")) if w_np is not None else None
+    D, npar = desc.n_state, (12 if desc.model == capi.MODEL_MARKOV6 else 8)
+    state = torch.empty((B, 2 * D + npar), dtype=torch.float64, device=dev)
+    g_params = torch.zeros((B, npar), dtype=torch.float64, device=dev)
+    g_y0 = torch.zeros((B, D), dtype=torch.float64, device=dev)
+    tiles = (B + 15) // 16
+    recf = lib.ionode_grad_record_floats(L, N) if need_w else 0
+    partf = lib.ionode_grad_partial_floats(L, N) if need_w else 0
+    budget = _bounded_budget(cfg.get("record_budget_bytes"), DEFAULT_RECORD_BUDGET, dev, 0.5)
+    acc = torch.zeros(partf, dtype=torch.float64, device=dev) if need_w else None
+    main = torch.cuda.current_stream(dev)
+    # Two-phase sweep (NN models; csrc/ionode_grad.hpp, DESIGN.md 5.4).  A stage's vector-Jacobian product is linear in its seed
+    # (a scalar per trajectory) and everything else it needs comes from the step's checkpoint: phase A
+    # (ionode_dopri5_backward_recompute) computes the UNIT-SEED products of every (tile, step) of a chunk at once on the whole
+    # chip, on its own stream, one chunk AHEAD of phase B (ionode_dopri5_backward_sweep: the sequential walk, adjoint algebra
+    # only, one wavefront per tile); the reduction of a finished chunk (ionode_grad_reduce_unit: records scaled by the seeds
+    # the walk wrote) runs on a third stream.  Records and packets are double-buffered.
+    two_phase = bool(cfg.get("two_phase", os.environ.get("IONODE_GRAD_ONE_PHASE", "0") != "1")) and image is not None
+    if fused and not two_phase:
+        raise capi.IonodeError("the fused sum-of-squares sweep of the NN models is two-phase only: use grad.solve for the one-phase sweep")
+    pkd = int(lib.ionode_grad_packet_doubles()) if two_phase else 0
+    chunk, n_buf, bounds = plan_backward_chunks(n_iter, tiles, recf, pkd, budget, need_w, two_phase)
+    records = [torch.empty(tiles * chunk * 6 * recf, dtype=torch.float32, device=dev) for _ in range(n_buf)] if need_w else [None] * n_buf
+    packets = [torch.empty(tiles * chunk * pkd, dtype=torch.float64, device=dev) for _ in range(n_buf)] if two_phase else [None] * n_buf
+    side = torch.cuda.Stream(dev) if (need_w and n_buf == 2) else main          # reductions
+    pre = torch.cuda.Stream(dev) if (two_phase and n_buf == 2) else main         # phase A
+    if pre is not main:
+        pre.wait_stream(main)    # gy (g_sse) / state / inputs were produced on the caller's stream
+    free = [None] * n_buf   # event: the reduce (or, without weight gradients, the walk) that last used this buffer pair has finished
+    ready = [None] * n_buf  # event: phase A has filled this buffer pair
+    desc.ckpt, desc.ckpt_cap = ckpt.data_ptr(), ckpt.shape[1]
+    sse_y0 = torch.zeros((B, D), dtype=torch.float64, device=dev) if fused else None   # sample-0 term of dL/dy0: written by the last chunk's G_c launch
+    common = (_ptr(image), _ptr(params), _ptr(cfg["prot_v"]), _ptr(cfg.get("prot_t")), _ptr(cfg.get("prot_of_traj")),
+              _ptr(cfg["t_eval"]), _ptr(n_acc))
+
+    def phase_a(k):
+        it0, it1 = bounds[k]
+        b = k % n_buf
+        if free[b] is not None:
+            pre.wait_event(free[b])
+        if fused:   # G_c of the objective (one wavefront per trajectory and step), then the products without grad_y: same stream, same packets
+            rc = lib.ionode_dopri5_backward_sse_gc(C.byref(desc), it0, it1, n_iter, *common[2:], _ptr(g_sse), _ptr(packets[b]), _ptr(sse_y0),
+                                                   C.c_void_p(pre.cuda_stream))
+            if rc != 0:
+                raise capi.IonodeError(f"ionode_dopri5_backward_sse_gc failed ({rc}): {lib.ionode_grad_last_error().decode()}")
+            rc = lib.ionode_dopri5_backward_recompute_sse(C.byref(desc), it0, it1, n_iter, *common, _ptr(records[b]), _ptr(packets[b]),
+                                                          C.c_void_p(pre.cuda_stream))
+        else:
+            rc = lib.ionode_dopri5_backward_recompute(C.byref(desc), it0, it1, n_iter, *common, _ptr(gy), _ptr(records[b]),
+                                                      _ptr(packets[b]), C.c_void_p(pre.cuda_stream))
+        if rc != 0:
+            raise capi.IonodeError(f"ionode_dopri5_backward_recompute failed ({rc}): {lib.ionode_grad_last_error().decode()}")
+        ev = torch.cuda.Event()
+        ev.record(pre)
+        ready[b] = ev
+
+    if two_phase:
+        phase_a(0)
+    for k, (it0, it1) in enumerate(bounds):
+        b = k % n_buf
+        rec = records[b]
+        if two_phase:
+            if k + 1 < len(bounds) and n_buf == 2:
+                phase_a(k + 1)                      # one chunk ahead, beside this chunk's walk
+            main.wait_event(ready[b])
+            walk = lib.ionode_dopri5_backward_sweep_sse if fused else lib.ionode_dopri5_backward_sweep
+            rc = walk(C.byref(desc), it0, it1, n_iter, *common, _ptr(sse_y0 if fused else gy), _ptr(state), _ptr(rec),
+                      _ptr(packets[b]), _ptr(g_params), _ptr(g_y0), C.c_void_p(main.cuda_stream))
+        else:
+            if free[b] is not None:
+                main.wait_event(free[b])
+            rc = lib.ionode_dopri5_backward(C.byref(desc), it0, it1, n_iter, *common, _ptr(gy), _ptr(state), _ptr(rec),
+                                            _ptr(g_params), _ptr(g_y0), C.c_void_p(main.cuda_stream))
+        if rc != 0:
+            raise capi.IonodeError(f"backward sweep failed ({rc}): {lib.ionode_grad_last_error().decode()}")
+        swept = torch.cuda.Event()
+        swept.record(main)
+        if need_w:
+            n_rec = tiles * (it1 - it0) * 6
+            n_slabs = int(os.environ.get("IONODE_GRAD_SLABS", 0)) or int(lib.ionode_grad_reduce_slabs(L, N, n_rec))   # one round of workgroups on this device (env: dev override for A/B runs)
+            side.wait_event(swept)
+            with torch.cuda.stream(side):
+                partials = torch.empty((n_slabs, partf), dtype=torch.float32, device=dev)
+                reduce = lib.ionode_grad_reduce_unit if two_phase else lib.ionode_grad_reduce   # unit-seed records: scaled while staged
+                rc = reduce(L, N, _ptr(rec), n_rec, n_slabs, _ptr(partials), C.c_void_p(side.cuda_stream))
+                if rc != 0:
+                    raise capi.IonodeError(f"ionode_grad_reduce failed ({rc}): {lib.ionode_grad_last_error().decode()}")
+                acc += partials.double().sum(0)
+                done = torch.cuda.Event()
+                done.record(side)
+            free[b] = done
+        else:
+            free[b] = swept
+        if two_phase and n_buf == 1 and k + 1 < len(bounds):
+            phase_a(k + 1)                          # single buffer: strictly alternate
+    if need_w and side is not main:
+        main.wait_stream(side)
+    if pre is not main:
+        main.wait_stream(pre)
+    return acc, g_params, g_y0
 
 
 def solve(model, weights_flat, params, prot_v, y0, t_eval, *, mlp_layers=0, mlp_width=0, prot_t=None, prot_t0=0.0,
@@ -438,6 +465,57 @@ class _SumOfSquares(torch.autograd.Function):
         return (g_params if ctx.needs_input_grad[0] else None), (g_y0.to(ctx.sdt) if ctx.needs_input_grad[1] else None), None
 
 
+class _SumOfSquaresNN(torch.autograd.Function):
+    """sse[B] of the fused forward for NN-f / NN-d; differentiable in (weights_flat, params, y0).  Forward: ionode_dopri5 with
+    checkpoints, sse_out and the packed weights, no state trace.  Backward: _Solve.backward's two-phase chunk loop (_sweep) with the
+    [B] upstream gradient -- ionode_dopri5_backward_sse_gc forms each chunk's G_c, the products run without grad_y."""
+
+    @staticmethod
+    def forward(ctx, weights_flat, params, y0, cfg):
+        dev = y0.device
+        B, D = y0.shape
+        L, N = cfg["mlp_layers"], cfg["mlp_width"]
+        w_np = weights_flat.detach().to(torch.float32).cpu().numpy()
+        from . import batched  # packed forward image: shared cache with the plain solve
+        packed = batched.packed_weights(w_np, L, N, dev, key=cfg.get("weights_key"))
+        r, ckpt, _most = _forward_with_checkpoints(lambda ckpt: capi.dopri5(
+            cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], mlp_packed=packed, mlp_layers=L, mlp_width=N,
+            prot_t=cfg["prot_t"], prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"], prot_of_traj=cfg["prot_of_traj"], rtol=cfg["rtol"],
+            atol=cfg["atol"], v_oob=cfg["v_oob"], max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"],
+            max_step=cfg["max_step"], ckpt=ckpt, obs_g=cfg["obs_g"], obs_e=cfg["obs_e"],
+            obs_open_state_only=cfg["obs_open_state_only"], t_eval_hint=cfg["t_eval_hint"],
+            sse_ref=cfg["sse_ref"], states=False), B, D, cfg, dev)
+        ctx.cfg, ctx.desc = cfg, r["desc"]
+        ctx.vtab = r["v_at_outputs"]   # (when the descriptor points at one, the backward reads V(t_k) from the same table)
+        ctx.w_np, ctx.sdt = w_np, y0.dtype
+        ctx.save_for_backward(params.detach(), ckpt, r["stats"], r["status"])
+        ctx.mark_non_differentiable(r["status"])
+        return r["sse"], r["status"]
+
+    @staticmethod
+    def backward(ctx, g_sse, _gstatus):
+        cfg, desc = ctx.cfg, ctx.desc
+        params, ckpt, stats, status = ctx.saved_tensors
+        failed = status != 0
+        # failed trajectories (sse = inf): their upstream rows are ignored and their gradient rows are zero
+        g = torch.where(failed, torch.zeros((), dtype=torch.float64, device=params.device), g_sse.to(torch.float64)).contiguous()
+        n_acc = torch.where(failed, torch.zeros_like(stats[:, 0]), stats[:, 0]).to(torch.int32).contiguous()
+        need_w = ctx.needs_input_grad[0]
+        vtab = None
+        if desc.v_at_outputs is None and 4 * desc.n_prot <= desc.n_traj:
+            # V(t_k) once per protocol ([P, Nt]) instead of one lookup per trajectory and sample: capi.dopri5's "auto" rule for the
+            # closed-form epilogue, here for the G_c kernel alone (the NN forward has formed its own voltages already)
+            vtab = capi.protocol_at_outputs(desc, cfg["prot_v"], cfg["prot_t"], cfg["t_eval"])
+            desc.v_at_outputs = vtab.data_ptr()
+        acc, g_params, g_y0 = _sweep(cfg, desc, ctx.w_np, need_w, params, ckpt, n_acc, g_sse=g)
+        g_params[failed] = 0.0
+        g_y0[failed] = 0.0
+        if vtab is not None:
+            desc.v_at_outputs = None   # (the table lives for this backward only)
+        g_w = unpack_partial(acc, cfg["mlp_layers"], cfg["mlp_width"]).to(torch.float32) if need_w else None
+        return g_w, (g_params if ctx.needs_input_grad[1] else None), (g_y0.to(ctx.sdt) if ctx.needs_input_grad[2] else None), None
+
+
 def uniform_grid_hint(t_eval):
     """(t0, dt) of a uniform output grid -- what the fused objective's output cursor needs (ionode_desc.t_eval_dt_hint; the
     kernel verifies it against t_eval) -- or None: capi.dopri5's "auto" rule (every t_k within dt / 2 of t0 + k dt)."""
@@ -453,9 +531,10 @@ def uniform_grid_hint(t_eval):
 
 def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, prot_t0=0.0, prot_dt=1.0, prot_of_traj=None,
                    obs_g=1.0, obs_e=-86.0, obs_open_state_only=False, rtol=1e-7, atol=1e-9, v_oob=-80.0, max_steps=0,
-                   max_total_steps=0, max_step=0.0, ckpt_cap=None, ckpt_budget_bytes=None):
-    """Fused sum-of-squares objective with its gradient (PINTS SumOfSquaresError.evaluateS1 over a batch; closed-form HH 2-state
-    and 6-state models).
+                   max_total_steps=0, max_step=0.0, ckpt_cap=None, ckpt_budget_bytes=None, weights_flat=None, mlp_layers=0, mlp_width=0,
+                   weights_key=None, record_budget_bytes=None, two_phase=None):
+    """Fused sum-of-squares objective with its gradient (PINTS SumOfSquaresError.evaluateS1 over a batch): the closed-form HH
+    2-state and 6-state models, and -- with weights_flat -- NN-f and NN-d of every width the backward sweep serves.
 
     sse[b] = sum_k (i_k - sse_ref[protocol(b)][k])^2, i_k = obs_g * gate(y_k) * (V(t_k) - obs_e), gate = y0 * y1 (or the last
     state with obs_open_state_only), k = 0 .. Nt - 1 (sample 0 is y0): the objective of batched.solve(sse_ref=..., states=False).
@@ -468,10 +547,26 @@ def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, p
     the per-trajectory sums only, and the backward sweep (ionode_dopri5_backward_sse) re-evaluates every output sample from the
     checkpoints and forms dL/dy_k in the kernel.  Memory: the checkpoints (sized, regrown and bounded by ckpt_cap /
     ckpt_budget_bytes as in grad.solve) plus O(B).  The output grid must be uniform (the fused forward's output cursor); for any
-    other t_eval use the materialised route, grad.solve followed by the sum of squares in torch.  max_step: as grad.solve."""
-    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
-        raise capi.IonodeError("grad.sum_of_squares: the fused objective gradient is built for the closed-form HH 2-state and 6-state "
-                               "models; for NN models use grad.solve and form the sum of squares in torch")
+    other t_eval use the materialised route, grad.solve followed by the sum of squares in torch.  max_step: as grad.solve.
+
+    NN-f / NN-d: weights_flat [n] fp32 (reference state-dict order, as grad.solve's; it may require grad), mlp_layers, mlp_width,
+    weights_key (the weight images' cache key) and record_budget_bytes as in grad.solve; params [B, 8], y0 [B, 2].  The result is
+    differentiable in weights_flat, params and y0.  The backward is grad.solve's two-phase sweep with the same chunking, streams and
+    reduction; per chunk ionode_dopri5_backward_sse_gc re-evaluates the steps' output samples from the checkpoints and hands their
+    sums to the walk, and the vector-Jacobian products run without an output gradient.  Memory: the checkpoints, the chunk's records
+    and packets (record_budget_bytes), O(B) -- nothing of size [B, Nt].  This route is two-phase only: with two_phase=False, or
+    IONODE_GRAD_ONE_PHASE=1 in the environment, it raises; the one-phase sweep serves the materialised route (grad.solve)."""
+    nn = model in (capi.MODEL_NNF, capi.MODEL_NND)
+    if not nn and model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
+        raise NotImplementedError("unknown model")
+    if nn and weights_flat is None:
+        raise capi.IonodeError("grad.sum_of_squares: only the closed-form models have no weights; an NN model needs weights_flat, "
+                               "mlp_layers and mlp_width")
+    if not nn and weights_flat is not None:
+        raise capi.IonodeError("the closed-form models have no MLP: pass weights_flat=None")
+    if nn and (os.environ.get("IONODE_GRAD_ONE_PHASE", "0") == "1" or (two_phase is not None and not two_phase)):
+        raise capi.IonodeError("grad.sum_of_squares: the fused sweep of the NN models is two-phase only (two_phase=False or "
+                               "IONODE_GRAD_ONE_PHASE=1 asks for the one-phase sweep); for that use grad.solve and form the sum of squares in torch")
     max_step = _resolve_max_step(model, params, prot_v, v_oob, max_step)
     if not (isinstance(y0, torch.Tensor) and y0.is_cuda):
         raise capi.IonodeError("no HIP tensors: the integrator and its backward sweep have no CPU path")
@@ -487,4 +582,8 @@ def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, p
                rtol=float(rtol), atol=float(atol), v_oob=float(v_oob), max_steps=int(max_steps), max_total_steps=int(max_total_steps),
                max_step=float(max_step), obs_g=float(obs_g), obs_e=float(obs_e), obs_open_state_only=bool(obs_open_state_only),
                t_eval_hint=hint, sse_ref=sse_ref, ckpt_cap=ckpt_cap, ckpt_budget_bytes=ckpt_budget_bytes)
+    if nn:
+        cfg.update(mlp_layers=int(mlp_layers), mlp_width=int(mlp_width), weights_key=weights_key, record_budget_bytes=record_budget_bytes,
+                   two_phase=True)
+        return _SumOfSquaresNN.apply(weights_flat, params, y0.contiguous(), cfg)
     return _SumOfSquares.apply(params, y0.contiguous(), cfg)
