@@ -33,6 +33,32 @@ EXPORTS = (
     "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh",
 )
 
+# the backward sweep's entry points: their buffers in ABI order -- between (d, it_begin, it_end, n_iter) and stream (include/ionode.h;
+# tests/test_grad_entry_checks.py compares the names with the header's).  argtypes are generated from it, sweep_launch() calls by it.
+SWEEP_BUFFERS = {
+    "ionode_dopri5_backward": ("grad_image", "params", "prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "grad_y", "state",
+                               "records", "grad_params", "grad_y0"),
+    "ionode_dopri5_backward_sse": ("params", "prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "grad_sse", "state",
+                                   "grad_params", "grad_y0"),
+    "ionode_dopri5_backward_recompute": ("grad_image", "params", "prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "grad_y",
+                                         "records", "packets"),
+    "ionode_dopri5_backward_sweep": ("grad_image", "params", "prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "grad_y", "state",
+                                     "records", "packets", "grad_params", "grad_y0"),
+    "ionode_dopri5_backward_sse_gc": ("prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "grad_sse", "packets", "sse_grad_y0"),
+    "ionode_dopri5_backward_recompute_sse": ("grad_image", "params", "prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "records",
+                                             "packets"),
+    "ionode_dopri5_backward_sweep_sse": ("grad_image", "params", "prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "sse_grad_y0",
+                                         "state", "records", "packets", "grad_params", "grad_y0"),
+}
+
+
+def n_state(model):
+    return 6 if model == MODEL_MARKOV6 else 2
+
+
+def n_params(model):
+    return 12 if model == MODEL_MARKOV6 else 8
+
 
 class IonodeDesc(C.Structure):
     _fields_ = [
@@ -96,23 +122,11 @@ def lib():
             fn.argtypes = [C.c_int32, C.c_int32]
         L.ionode_grad_pack.restype = C.c_int
         L.ionode_grad_pack.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        L.ionode_dopri5_backward.restype = C.c_int
-        L.ionode_dopri5_backward.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 13
-        L.ionode_dopri5_backward_sse.restype = C.c_int
-        L.ionode_dopri5_backward_sse.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11
-        L.ionode_dopri5_backward_recompute.restype = C.c_int
         L.ionode_grad_packet_doubles.restype = C.c_size_t
         L.ionode_grad_packet_doubles.argtypes = []
-        L.ionode_dopri5_backward_recompute.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 11
-        L.ionode_dopri5_backward_sweep.restype = C.c_int
-        L.ionode_dopri5_backward_sweep.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 14
-        # the fused sum-of-squares objective on the two-phase sweep (NN-f / NN-d)
-        L.ionode_dopri5_backward_sse_gc.restype = C.c_int
-        L.ionode_dopri5_backward_sse_gc.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 9
-        L.ionode_dopri5_backward_recompute_sse.restype = C.c_int
-        L.ionode_dopri5_backward_recompute_sse.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 10
-        L.ionode_dopri5_backward_sweep_sse.restype = C.c_int
-        L.ionode_dopri5_backward_sweep_sse.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 14
+        for name, buffers in SWEEP_BUFFERS.items():
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * (len(buffers) + 1)
         L.ionode_grad_reduce.restype = C.c_int
         L.ionode_grad_reduce.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.ionode_grad_reduce_slabs.restype = C.c_int32
@@ -261,16 +275,9 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
     # output-grid hint (t0, dt): a guess the kernel verifies against t_eval; "auto" derives it from the end points
     # (one tiny device->host read), None disables it (cooperative scan)
     if isinstance(t_eval_hint, str) and t_eval_hint == "auto":
-        t_eval_hint = None
-        if Nt > 1:
-            t0h = t_eval[0]
-            dth = (t_eval[Nt - 1] - t0h) / (Nt - 1)
-            dev_ = (t_eval - (t0h + torch.arange(Nt, dtype=torch.float64, device=t_eval.device) * dth)).abs().max()
-            vals = torch.stack([t0h, dth, dev_]).cpu()  # one small device->host read; pass t_eval_hint=(t0, dt) to avoid it
-            if float(vals[1]) > 0 and float(vals[2]) <= 0.5 * float(vals[1]):
-                t_eval_hint = (float(vals[0]), float(vals[1]))
-                if t_eval_exact is None:
-                    t_eval_exact = float(vals[2]) == 0.0
+        t_eval_hint = uniform_grid(t_eval)   # pass t_eval_hint=(t0, dt) to avoid its device->host read
+        if t_eval_hint is not None and t_eval_exact is None:
+            t_eval_exact = t_eval_hint[2] == 0.0
     if t_eval_hint is not None and t_eval_hint[1] > 0:
         desc.t_eval_t0_hint, desc.t_eval_dt_hint = float(t_eval_hint[0]), float(t_eval_hint[1])
         if t_eval_exact is None:
@@ -354,6 +361,32 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
         raise IonodeError(f"ionode_dopri5 failed ({rc}): {last_error()}")
     return {"y": y, "i": i_out, "status": status, "stats": st, "sse": sse, "desc": desc, "v_at_outputs": vtab,
             "kernel": lib().ionode_last_kernel_name().decode()}
+
+
+def uniform_grid(t_eval):
+    """(t0, dt, largest |t_k - (t0 + k dt)|) of an output grid that is uniform -- dt > 0 from the end points, every t_k within dt / 2 of
+    its place -- or None.  One small device->host read."""
+    n = int(t_eval.shape[0])
+    if n < 2:
+        return None
+    t0 = t_eval[0]
+    dt = (t_eval[n - 1] - t0) / (n - 1)
+    dev = (t_eval - (t0 + torch.arange(n, dtype=torch.float64, device=t_eval.device) * dt)).abs().max()
+    t0, dt, dev = (float(x) for x in torch.stack([t0, dt, dev]).cpu())
+    return (t0, dt, dev) if dt > 0 and dev <= 0.5 * dt else None
+
+
+def sweep_launch(name, desc, it_begin, it_end, n_iter, stream, **buffers):
+    """Call the backward-sweep entry point `name` on iterations [it_begin, it_end) with its buffers BY NAME: exactly the names of
+    SWEEP_BUFFERS[name], each a device tensor or None (NULL); `stream` is a torch stream.  Raises IonodeError with the return code and
+    ionode_grad_last_error()."""
+    names = SWEEP_BUFFERS[name]
+    if set(buffers) != set(names):
+        raise TypeError(f"{name}: missing {sorted(set(names) - set(buffers))}, unknown {sorted(set(buffers) - set(names))}")
+    ptrs = [None if buffers[n] is None else C.c_void_p(buffers[n].data_ptr()) for n in names]
+    rc = getattr(lib(), name)(C.byref(desc), it_begin, it_end, n_iter, *ptrs, C.c_void_p(stream.cuda_stream))
+    if rc != 0:
+        raise IonodeError(f"{name} failed ({rc}): {lib().ionode_grad_last_error().decode()}")
 
 
 def protocol_at_outputs(desc, prot_v, prot_t, t_eval, stream=None):

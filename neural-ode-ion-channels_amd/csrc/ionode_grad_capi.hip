@@ -1,5 +1,6 @@
 // ionode_grad_capi.hip -- C ABI of the gradient path (include/ionode.h, "gradients through the solve"): the grad image
 // packer, the backward-sweep launcher and the weight-gradient reduction launcher.
+#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 
@@ -9,7 +10,14 @@
 namespace {
 
 thread_local char g_gerr[256] = "";
-void gerr(const char *m) { snprintf(g_gerr, sizeof g_gerr, "%s", m); }
+__attribute__((format(printf, 2, 3))) int refuse(int rc, const char *fmt, ...) {   // sets ionode_grad_last_error(), returns rc
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_gerr, sizeof g_gerr, fmt, ap);
+  va_end(ap);
+  return rc;
+}
+void gerr(const char *m) { refuse(0, "%s", m); }
 
 inline int np_of(int N) { return 16 * ((N + 15) / 16); }
 
@@ -17,52 +25,158 @@ using ionode::GArgs;
 using ionode::Sweep;
 using ionode::SweepFn;
 
-// launchers that have no width: the closed-form models' sweeps (NT = 1, unused) and the NN models' walk
+// launchers that have no width: the closed-form models' sweeps (NT = 1, unused), the NN models' walk and their G_c kernel
 template <int MODEL> SweepFn closed_sweep(int f32) { return f32 ? &ionode::launch_sweep<MODEL, float, 1> : &ionode::launch_sweep<MODEL, double, 1>; }
 template <int MODEL> SweepFn closed_sweep_sse(int f32) { return f32 ? &ionode::launch_sweep_sse<MODEL, float> : &ionode::launch_sweep_sse<MODEL, double>; }
 inline SweepFn sse_gc(int f32) { return f32 ? &ionode::launch_sse_gc<float> : &ionode::launch_sse_gc<double>; }
 template <int MODEL> SweepFn walk(int f32) { return f32 ? &ionode::launch_walk<MODEL, float> : &ionode::launch_walk<MODEL, double>; }
 
-// nullptr: no variant of that width (a width without a sweep has no walk either, though the walk kernel itself has no width)
-SweepFn find_sweep(Sweep which, int model, int f32, int NT) {
-  if (which == Sweep::Walk) {
-    if (!ionode::for_width(NT, [](auto) {}, [] {})) return nullptr;
-    return model == IONODE_MODEL_NNF ? walk<IONODE_MODEL_NNF>(f32) : walk<IONODE_MODEL_NND>(f32);
-  }
-  const bool recompute = which == Sweep::Recompute;
-  SweepFn fn = nullptr;
-  ionode::for_width(NT, [&](auto nt) { fn = ionode::pick_sweep<decltype(nt)::value>(recompute, model, f32); },
-                    [&] { fn = ionode::pick_sweep32(recompute, model, f32); });   // inst_grad32.hip
-  return fn;
-}
-
-// ---- what every sweep entry point shares: the descriptor's consistency, and the argument block filled from it ----
 inline bool is_m6(const ionode_desc *d) { return d->model == IONODE_MODEL_MARKOV6; }
+inline bool is_nn(const ionode_desc *d) { return d->model == IONODE_MODEL_NNF || d->model == IONODE_MODEL_NND; }
 inline bool desc_consistent(const ionode_desc *d) {
   const bool m6 = is_m6(d);
   return !(d->n_state != (m6 ? 6 : 2) || d->n_traj < 1 || d->n_out < 1 || d->n_prot < 1 || d->prot_n < 2 || d->n_params < (m6 ? 12 : 8) || !(d->prot_dt > 0));
 }
-inline bool bad_range(int32_t it_begin, int32_t it_end, int32_t n_iter) { return it_begin < 0 || it_end <= it_begin || it_end > n_iter; }
 
-// (L, NP): the net; closed-form models: (0, 16)
-GArgs fill_args(const ionode_desc *d, int L, int NP, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *params,
-                const double *prot_v, const double *prot_t, const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
-                double *state, double *grad_params, double *grad_y0) {
-  GArgs a;
-  memset(&a, 0, sizeof a);
-  a.k.params = params; a.k.prot_v = prot_v; a.k.prot_t = prot_t; a.k.prot_of_traj = prot_of_traj; a.k.t_eval = t_eval;
-  a.k.B = d->n_traj; a.k.Nt = d->n_out; a.k.P = d->n_prot; a.k.Np = d->prot_n; a.k.n_params = d->n_params;
-  a.k.L = L; a.k.NP = NP; a.k.NT = NP / 16;
-  a.k.prot_t0 = d->prot_t0; a.k.prot_dt = d->prot_dt; a.k.prot_rdt = 1.0 / d->prot_dt; a.k.v_oob = d->v_oob;
-  a.ckpt = d->ckpt; a.ckpt_cap = d->ckpt_cap; a.nacc = n_accepted; a.state = state; a.grad_params = grad_params; a.grad_y0 = grad_y0;
-  a.it_begin = it_begin; a.it_end = it_end; a.n_iter = n_iter;
-  return a;
+// nullptr: no variant of that width (a width without a sweep has no walk and no G_c launch either, though those kernels have no width)
+// (Not a correctness rule: the branches may come in any order.  This one -- walk, sweep / recompute, closed-form, G_c -- is the order
+// the launchers were first used in before, so the kernels are emitted where they were and the code objects compare equal byte for byte.)
+SweepFn find_sweep(Sweep which, const ionode_desc *d, int NT) {
+  const int f32 = d->state_f32 ? 1 : 0;
+  const bool nn = is_nn(d), m6 = is_m6(d);
+  if (nn && which == Sweep::Walk) {
+    if (!ionode::for_width(NT, [](auto) {}, [] {})) return nullptr;
+    return d->model == IONODE_MODEL_NNF ? walk<IONODE_MODEL_NNF>(f32) : walk<IONODE_MODEL_NND>(f32);
+  }
+  if (nn && which != Sweep::SseGc) {
+    const bool recompute = which == Sweep::Recompute;
+    SweepFn fn = nullptr;
+    ionode::for_width(NT, [&](auto nt) { fn = ionode::pick_sweep<decltype(nt)::value>(recompute, d->model, f32); },
+                      [&] { fn = ionode::pick_sweep32(recompute, d->model, f32); });   // inst_grad32.hip
+    return fn;
+  }
+  if (!nn && which != Sweep::ClosedSse) return m6 ? closed_sweep<IONODE_MODEL_MARKOV6>(f32) : closed_sweep<IONODE_MODEL_HH2>(f32);
+  if (!nn) return m6 ? closed_sweep_sse<IONODE_MODEL_MARKOV6>(f32) : closed_sweep_sse<IONODE_MODEL_HH2>(f32);
+  return ionode::for_width(NT, [](auto) {}, [] {}) ? sse_gc(f32) : nullptr;
 }
 
-int launch(SweepFn fn, const GArgs &a, size_t lds, void *stream) {
-  fn(a, (unsigned)((a.k.B + 15) / 16), lds, reinterpret_cast<hipStream_t>(stream));
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) { gerr(hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
+// ---- the seven sweep entry points: one block of named arguments, one Entry row each, one checked launch ----
+// What an entry point received, by the names of include/ionode.h; what it does not have stays NULL.
+struct Buffers {
+  int32_t it_begin, it_end, n_iter;
+  const float *grad_image;
+  const double *params, *prot_v, *prot_t;
+  const int32_t *prot_of_traj;
+  const double *t_eval;
+  const int32_t *n_accepted;
+  const void *grad_y;
+  const double *grad_sse;
+  double *sse_grad_y0, *state;
+  float *records;
+  double *packets, *grad_params, *grad_y0;
+  void *stream;
+};
+
+enum class Family { Any, Closed, NN };
+// Where the checks that move sit (checked_launch writes the order down); tests/golden/grad_entry_checks.json pins all three.
+//   Oldest     packets, then the family; buffers before the range, grid.y behind it; traj_per_image behind those
+//   SseClosed  family, traj_per_image; buffers before the range
+//   SseNN      family, traj_per_image; packets, buffers and grid.y last, behind the MLP shape
+enum class Order { Oldest, SseClosed, SseNN };
+
+constexpr const char *OLDEST_NULL = "ionode_dopri5_backward: required buffer is NULL (ckpt / ckpt_cap come from the descriptor)";
+constexpr const char *SSE_NULL = "%s: required buffer is NULL (sse_ref / ckpt / ckpt_cap come from the descriptor)";
+constexpr const char *RECOMPUTE = "ionode_dopri5_backward_recompute";
+
+struct Entry {
+  const char *name;          // in messages
+  Family family;             // the models it serves
+  Order order;
+  Sweep launch;              // how find_sweep picks the launcher; the LDS bytes follow the model (closed-form: G_c scratch, NN: the net's; SseGc: none)
+  bool sse_ref;              // reads d->sse_ref: the sum-of-squares fields of GArgs are filled
+  const char *grid_y_who;    // grid.y = ceil(iterations / 4), at most 65535 x 4 iterations per launch: the name its refusal carries; nullptr: no cap
+  const char *buffers_null;  // the text for a missing pointer argument (%s: name); the _sse forms of recompute and walk answer as those do
+  bool (*has_buffers)(const Buffers &);   // its required pointers beyond prot_v, t_eval, n_accepted (all), grad_image (NN models, every
+                                          // launch but SseGc) and packets (Recompute, Walk)
+};
+static_assert(ionode::GRAD_RECOMPUTE_IB == 4 && ionode::GRAD_GC_WAVES == 4, "Entry::grid_y_who");
+
+inline bool adjoint(const Buffers &b) { return b.state && b.grad_params && b.grad_y0; }   // a launch that reads and writes the adjoint state
+const Entry BACKWARD = {"ionode_dopri5_backward", Family::Any, Order::Oldest, Sweep::OnePhase, false, nullptr, OLDEST_NULL,
+                        [](const Buffers &b) { return b.params && b.grad_y && adjoint(b); }};
+const Entry BACKWARD_SSE = {"ionode_dopri5_backward_sse", Family::Closed, Order::SseClosed, Sweep::ClosedSse, true, nullptr, SSE_NULL,
+                            [](const Buffers &b) { return b.params && b.grad_sse && adjoint(b); }};
+const Entry BACKWARD_RECOMPUTE = {RECOMPUTE, Family::NN, Order::Oldest, Sweep::Recompute, false, RECOMPUTE, OLDEST_NULL,
+                                  [](const Buffers &b) { return b.params && b.grad_y; }};
+const Entry BACKWARD_SWEEP = {"ionode_dopri5_backward_sweep", Family::NN, Order::Oldest, Sweep::Walk, false, nullptr, OLDEST_NULL,
+                              [](const Buffers &b) { return b.params && b.grad_y && adjoint(b); }};
+const Entry SSE_GC = {"ionode_dopri5_backward_sse_gc", Family::NN, Order::SseNN, Sweep::SseGc, true, "ionode_dopri5_backward_sse_gc",
+                      "%s: required buffer is NULL", [](const Buffers &b) { return b.grad_sse && b.packets && b.sse_grad_y0; }};
+const Entry RECOMPUTE_SSE = {"ionode_dopri5_backward_recompute_sse", Family::NN, Order::SseNN, Sweep::Recompute, true, RECOMPUTE, OLDEST_NULL,
+                             [](const Buffers &b) { return b.params != nullptr; }};
+const Entry SWEEP_SSE = {"ionode_dopri5_backward_sweep_sse", Family::NN, Order::SseNN, Sweep::Walk, true, nullptr, OLDEST_NULL,
+                         [](const Buffers &b) { return b.params && b.sse_grad_y0 && adjoint(b); }};
+
+int checked_launch(const Entry &e, const ionode_desc *d, const Buffers &b) {
+  constexpr const char *TWO_PHASE = "two-phase sweep: NN-f / NN-d only, `packets` required";
+  constexpr const char *VARIANTS = "backward sweep: (L, N) outside the compiled variants (N pads to 16, 112, 208 or 512; at most 15 hidden layers)";
+  if (!d) return refuse(IONODE_ERR_ARG, "null descriptor");
+  const bool oldest = e.order == Order::Oldest, last = e.order == Order::SseNN;
+  const bool nn = is_nn(d), two_phase = e.launch == Sweep::Recompute || e.launch == Sweep::Walk;
+  // the three checks whose place depends on e.order
+  auto packets = [&] { return two_phase && !b.packets ? refuse(IONODE_ERR_ARG, TWO_PHASE) : 0; };
+  auto buffers = [&] {
+    if (b.prot_v && b.t_eval && b.n_accepted && (b.grad_image || !nn || e.launch == Sweep::SseGc) && e.has_buffers(b)) return 0;
+    return refuse(IONODE_ERR_ARG, e.buffers_null, e.name);
+  };
+  auto grid_y = [&] {
+    if (!e.grid_y_who || (int64_t)b.it_end - b.it_begin <= (int64_t)65535 * 4) return 0;
+    return refuse(IONODE_ERR_ARG, "%s: at most 65535 x 4 iterations per launch (HIP's grid.y limit): split the range", e.grid_y_who);
+  };
+  auto one_image = [&] {
+    if (d->traj_per_image <= 0) return 0;
+    return oldest ? refuse(IONODE_ERR_UNSUPPORTED, "backward sweep: one weight set per launch (traj_per_image must be 0)")
+                  : refuse(IONODE_ERR_UNSUPPORTED, "%s: traj_per_image must be 0", e.name);
+  };
+  int rc;
+  if (!last && (rc = packets())) return rc;
+  if (e.family == Family::NN && !nn)
+    return oldest ? refuse(IONODE_ERR_ARG, TWO_PHASE) : refuse(IONODE_ERR_UNSUPPORTED, "%s: NN-f / NN-d only (closed-form models: ionode_dopri5_backward_sse)", e.name);
+  if (e.family == Family::Closed && d->model != IONODE_MODEL_HH2 && !is_m6(d)) return refuse(IONODE_ERR_UNSUPPORTED, "%s: closed-form models only (HH 2-state, 6-state)", e.name);
+  if (!oldest && (rc = one_image())) return rc;
+  if (d->model < 0 || d->model > 3) return refuse(IONODE_ERR_UNSUPPORTED, "backward sweep: unknown model");
+  if (!desc_consistent(d)) return refuse(IONODE_ERR_ARG, "inconsistent descriptor");
+  if ((e.sse_ref && !d->sse_ref) || !d->ckpt || d->ckpt_cap < 1) return oldest ? refuse(IONODE_ERR_ARG, OLDEST_NULL) : refuse(IONODE_ERR_ARG, SSE_NULL, e.name);
+  if (!last && (rc = buffers())) return rc;
+  if (b.it_begin < 0 || b.it_end <= b.it_begin || b.it_end > b.n_iter) return refuse(IONODE_ERR_ARG, "bad iteration range");
+  if (!last && (rc = grid_y())) return rc;
+  if (oldest && (rc = one_image())) return rc;
+  if (nn && (d->mlp_layers < 1 || d->mlp_width < 1)) return refuse(IONODE_ERR_ARG, "bad MLP shape");
+  const int NP = nn ? np_of(d->mlp_width) : 16, NT = NP / 16, L = nn ? d->mlp_layers : 0;   // closed-form models: (0, 16)
+  const SweepFn fn = find_sweep(e.launch, d, NT);
+  const size_t net_lds = ionode::grad_lds_bytes(L, NT), walk_lds = net_lds + 16 + ionode::grad_walk_lds_bytes();   // (what a recompute launch's walk needs)
+  const size_t lds = !nn ? ionode::grad_closed_lds_bytes(d->n_state) : e.launch == Sweep::SseGc ? 0 : net_lds;
+  if (!fn || L > 15 || (nn && (oldest ? net_lds : walk_lds) > 160 * 1024)) return refuse(IONODE_ERR_UNSUPPORTED, VARIANTS);
+  if (two_phase && walk_lds > 160 * 1024) return refuse(IONODE_ERR_UNSUPPORTED, "two-phase sweep: LDS");
+  if (last && ((rc = packets()) || (rc = buffers()) || (rc = grid_y()))) return rc;
+
+  GArgs a;
+  memset(&a, 0, sizeof a);
+  a.k.params = b.params; a.k.prot_v = b.prot_v; a.k.prot_t = b.prot_t; a.k.prot_of_traj = b.prot_of_traj; a.k.t_eval = b.t_eval;
+  a.k.B = d->n_traj; a.k.Nt = d->n_out; a.k.P = d->n_prot; a.k.Np = d->prot_n; a.k.n_params = d->n_params;
+  a.k.L = L; a.k.N = d->mlp_width; a.k.NP = NP; a.k.NT = NT;
+  a.k.prot_t0 = d->prot_t0; a.k.prot_dt = d->prot_dt; a.k.prot_rdt = 1.0 / d->prot_dt; a.k.v_oob = d->v_oob;
+  a.img = b.grad_image; a.ckpt = d->ckpt; a.ckpt_cap = d->ckpt_cap; a.nacc = b.n_accepted; a.grad_y = b.grad_y; a.state = b.state;
+  a.records = nn ? b.records : nullptr; a.record_floats = ionode::grad_record_floats(L, NT); a.packets = b.packets;
+  a.grad_params = b.grad_params; a.grad_y0 = b.grad_y0; a.sse_y0 = b.sse_grad_y0;
+  a.it_begin = b.it_begin; a.it_end = b.it_end; a.n_iter = b.n_iter;
+  if (e.sse_ref) {
+    a.grad_sse = b.grad_sse; a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
+    a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
+  }
+  fn(a, (unsigned)((a.k.B + 15) / 16), lds, reinterpret_cast<hipStream_t>(b.stream));
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return refuse(IONODE_ERR_LAUNCH, "%s", hipGetErrorString(err));
   return IONODE_OK;
 }
 
@@ -120,88 +234,41 @@ int ionode_grad_pack(const float *w, int32_t L, int32_t N, float *out) {
   return IONODE_OK;
 }
 
-// One-phase sweep, or phase A (Recompute: the unit-seed products and packets of every (tile, step)) / phase B (Walk) of the two-phase
-// sweep.  Phase A carries no adjoint state: it requires neither `state` nor the gradient outputs.
-static int backward_impl(Sweep which, const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
-                         const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
-                         const double *t_eval, const int32_t *n_accepted, const void *grad_y, double *state,
-                         float *records, double *packets, double *grad_params, double *grad_y0, void *stream,
-                         bool fused = false, const double *sse_y0 = nullptr) {
-  // fused (two-phase only): the sum-of-squares objective -- no grad_y; the walk reads the sample-0 term of dL/dy0 from sse_y0
-  if (!d) { gerr("null descriptor"); return IONODE_ERR_ARG; }
-  const bool two_phase = which != Sweep::OnePhase;
-  if (two_phase && (!packets || (d->model != IONODE_MODEL_NNF && d->model != IONODE_MODEL_NND))) {
-    gerr("two-phase sweep: NN-f / NN-d only, `packets` required"); return IONODE_ERR_ARG;
-  }
-  const bool m6 = is_m6(d);
-  const bool closed = d->model == IONODE_MODEL_HH2 || m6;  // closed-form models: no MLP image, no records
-  if (d->model < 0 || d->model > 3) { gerr("backward sweep: unknown model"); return IONODE_ERR_UNSUPPORTED; }
-  if (!desc_consistent(d)) { gerr("inconsistent descriptor"); return IONODE_ERR_ARG; }
-  const bool adjoint = which != Sweep::Recompute;   // the launch reads and writes the adjoint state
-  if ((!grad_image && !closed) || !params || !prot_v || !t_eval || !n_accepted || (fused ? (which == Sweep::Walk && !sse_y0) : !grad_y) || (adjoint && (!state || !grad_params || !grad_y0)) || !d->ckpt || d->ckpt_cap < 1) {
-    gerr("ionode_dopri5_backward: required buffer is NULL (ckpt / ckpt_cap come from the descriptor)"); return IONODE_ERR_ARG;
-  }
-  if (bad_range(it_begin, it_end, n_iter)) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
-  if (which == Sweep::Recompute && (int64_t)it_end - it_begin > (int64_t)65535 * ionode::GRAD_RECOMPUTE_IB) {
-    gerr("ionode_dopri5_backward_recompute: at most 65535 x 4 iterations per launch (HIP's grid.y limit): split the range");
-    return IONODE_ERR_ARG;
-  }
-  if (d->traj_per_image > 0) { gerr("backward sweep: one weight set per launch (traj_per_image must be 0)"); return IONODE_ERR_UNSUPPORTED; }
-  if (!closed && (d->mlp_layers < 1 || d->mlp_width < 1)) { gerr("bad MLP shape"); return IONODE_ERR_ARG; }
-  const int NP = closed ? 16 : np_of(d->mlp_width), NT = NP / 16, L = closed ? 0 : d->mlp_layers;
-  SweepFn fn = m6 ? closed_sweep<IONODE_MODEL_MARKOV6>(d->state_f32) : closed ? closed_sweep<IONODE_MODEL_HH2>(d->state_f32)
-                                                                            : find_sweep(which, d->model, d->state_f32 ? 1 : 0, NT);
-  const size_t lds = closed ? ionode::grad_closed_lds_bytes(d->n_state) : ionode::grad_lds_bytes(L, NT);
-  if (!fn || lds > 160 * 1024 || L > 15) {
-    gerr("backward sweep: (L, N) outside the compiled variants (N pads to 16, 112, 208 or 512; at most 15 hidden layers)");
-    return IONODE_ERR_UNSUPPORTED;
-  }
-  GArgs a = fill_args(d, L, NP, it_begin, it_end, n_iter, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, state, grad_params, grad_y0);
-  a.k.N = d->mlp_width; a.img = grad_image; a.grad_y = fused ? nullptr : grad_y; a.sse_y0 = const_cast<double *>(sse_y0);
-  a.records = closed ? nullptr : records;
-  a.record_floats = ionode::grad_record_floats(L, NT);
-  a.packets = two_phase ? packets : nullptr;
-  if (two_phase && ionode::grad_lds_bytes(L, NT) + 16 + ionode::grad_walk_lds_bytes() > 160 * 1024) { gerr("two-phase sweep: LDS"); return IONODE_ERR_UNSUPPORTED; }
-  return launch(fn, a, lds, stream);
-}
-
+// The sweep entry points (include/ionode.h): each names what it received and hands it to checked_launch with its row of the table above.
 int ionode_dopri5_backward(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
                            const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                            const double *t_eval, const int32_t *n_accepted, const void *grad_y, double *state,
                            float *records, double *grad_params, double *grad_y0, void *stream) {
-  return backward_impl(Sweep::OnePhase, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
-                       state, records, nullptr, grad_params, grad_y0, stream);
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.grad_image = grad_image; b.params = params; b.prot_v = prot_v;
+  b.prot_t = prot_t; b.prot_of_traj = prot_of_traj; b.t_eval = t_eval; b.n_accepted = n_accepted; b.grad_y = grad_y; b.state = state;
+  b.records = records; b.grad_params = grad_params; b.grad_y0 = grad_y0; b.stream = stream;
+  return checked_launch(BACKWARD, d, b);
 }
 
 int ionode_dopri5_backward_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *params,
                                const double *prot_v, const double *prot_t, const int32_t *prot_of_traj, const double *t_eval,
                                const int32_t *n_accepted, const double *grad_sse, double *state, double *grad_params,
                                double *grad_y0, void *stream) {
-  if (!d) { gerr("null descriptor"); return IONODE_ERR_ARG; }
-  if (d->model != IONODE_MODEL_HH2 && d->model != IONODE_MODEL_MARKOV6) {
-    gerr("ionode_dopri5_backward_sse: closed-form models only (HH 2-state, 6-state)"); return IONODE_ERR_UNSUPPORTED;
-  }
-  if (d->traj_per_image > 0) { gerr("ionode_dopri5_backward_sse: traj_per_image must be 0"); return IONODE_ERR_UNSUPPORTED; }
-  if (!desc_consistent(d)) { gerr("inconsistent descriptor"); return IONODE_ERR_ARG; }
-  if (!d->sse_ref || !grad_sse || !d->ckpt || d->ckpt_cap < 1 || !params || !prot_v || !t_eval || !n_accepted || !state || !grad_params || !grad_y0) {
-    gerr("ionode_dopri5_backward_sse: required buffer is NULL (sse_ref / ckpt / ckpt_cap come from the descriptor)"); return IONODE_ERR_ARG;
-  }
-  if (bad_range(it_begin, it_end, n_iter)) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
-  GArgs a = fill_args(d, 0, 16, it_begin, it_end, n_iter, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, state, grad_params, grad_y0);
-  a.grad_sse = grad_sse; a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
-  a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
-  SweepFn fn = is_m6(d) ? closed_sweep_sse<IONODE_MODEL_MARKOV6>(d->state_f32) : closed_sweep_sse<IONODE_MODEL_HH2>(d->state_f32);
-  return launch(fn, a, ionode::grad_closed_lds_bytes(d->n_state), stream);
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.params = params; b.prot_v = prot_v; b.prot_t = prot_t;
+  b.prot_of_traj = prot_of_traj; b.t_eval = t_eval; b.n_accepted = n_accepted; b.grad_sse = grad_sse; b.state = state;
+  b.grad_params = grad_params; b.grad_y0 = grad_y0; b.stream = stream;
+  return checked_launch(BACKWARD_SSE, d, b);
 }
 
 size_t ionode_grad_packet_doubles(void) { return (size_t)16 * ionode::GRAD_PACKET; }
 
+// Phase A (the unit-seed products and packets of every (tile, step)) carries no adjoint state; phase B is the walk.
 int ionode_dopri5_backward_recompute(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
                                      const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                                      const double *t_eval, const int32_t *n_accepted, const void *grad_y, float *records,
                                      double *packets, void *stream) {
-  return backward_impl(Sweep::Recompute, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
-                       nullptr, records, packets, nullptr, nullptr, stream);
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.grad_image = grad_image; b.params = params; b.prot_v = prot_v;
+  b.prot_t = prot_t; b.prot_of_traj = prot_of_traj; b.t_eval = t_eval; b.n_accepted = n_accepted; b.grad_y = grad_y;
+  b.records = records; b.packets = packets; b.stream = stream;
+  return checked_launch(BACKWARD_RECOMPUTE, d, b);
 }
 
 int ionode_dopri5_backward_sweep(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
@@ -209,70 +276,43 @@ int ionode_dopri5_backward_sweep(const ionode_desc *d, int32_t it_begin, int32_t
                                  const double *t_eval, const int32_t *n_accepted, const void *grad_y, double *state,
                                  float *records, const double *packets, double *grad_params, double *grad_y0,
                                  void *stream) {
-  return backward_impl(Sweep::Walk, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, grad_y,
-                       state, records, const_cast<double *>(packets), grad_params, grad_y0, stream);
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.grad_image = grad_image; b.params = params; b.prot_v = prot_v;
+  b.prot_t = prot_t; b.prot_of_traj = prot_of_traj; b.t_eval = t_eval; b.n_accepted = n_accepted; b.grad_y = grad_y; b.state = state;
+  b.records = records; b.packets = const_cast<double *>(packets); b.grad_params = grad_params; b.grad_y0 = grad_y0; b.stream = stream;
+  return checked_launch(BACKWARD_SWEEP, d, b);
 }
 
 // ---- the fused sum-of-squares objective on the two-phase sweep (NN-f / NN-d) ----
-// what the three entry points check first, in ionode_dopri5_backward_sse's order; nothing is launched before it passes
-static int sse_nn_check(const char *who, const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter) {
-  char m[200];
-  if (!d) { gerr("null descriptor"); return IONODE_ERR_ARG; }
-  if (d->model != IONODE_MODEL_NNF && d->model != IONODE_MODEL_NND) {
-    snprintf(m, sizeof m, "%s: NN-f / NN-d only (closed-form models: ionode_dopri5_backward_sse)", who); gerr(m); return IONODE_ERR_UNSUPPORTED;
-  }
-  if (d->traj_per_image > 0) { snprintf(m, sizeof m, "%s: traj_per_image must be 0", who); gerr(m); return IONODE_ERR_UNSUPPORTED; }
-  if (!desc_consistent(d)) { gerr("inconsistent descriptor"); return IONODE_ERR_ARG; }
-  if (!d->sse_ref || !d->ckpt || d->ckpt_cap < 1) {
-    snprintf(m, sizeof m, "%s: required buffer is NULL (sse_ref / ckpt / ckpt_cap come from the descriptor)", who); gerr(m); return IONODE_ERR_ARG;
-  }
-  if (bad_range(it_begin, it_end, n_iter)) { gerr("bad iteration range"); return IONODE_ERR_ARG; }
-  if (d->mlp_layers < 1 || d->mlp_width < 1) { gerr("bad MLP shape"); return IONODE_ERR_ARG; }
-  const int NT = np_of(d->mlp_width) / 16;
-  if (!find_sweep(Sweep::Walk, d->model, d->state_f32 ? 1 : 0, NT) || d->mlp_layers > 15 ||
-      ionode::grad_lds_bytes(d->mlp_layers, NT) + 16 + ionode::grad_walk_lds_bytes() > 160 * 1024) {
-    gerr("backward sweep: (L, N) outside the compiled variants (N pads to 16, 112, 208 or 512; at most 15 hidden layers)");
-    return IONODE_ERR_UNSUPPORTED;
-  }
-  return IONODE_OK;
-}
-
 int ionode_dopri5_backward_sse_gc(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *prot_v,
                                   const double *prot_t, const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
                                   const double *grad_sse, double *packets, double *sse_grad_y0, void *stream) {
-  const int rc = sse_nn_check("ionode_dopri5_backward_sse_gc", d, it_begin, it_end, n_iter);
-  if (rc != IONODE_OK) return rc;
-  if (!grad_sse || !prot_v || !t_eval || !n_accepted || !packets || !sse_grad_y0) {
-    gerr("ionode_dopri5_backward_sse_gc: required buffer is NULL"); return IONODE_ERR_ARG;
-  }
-  if ((int64_t)it_end - it_begin > (int64_t)65535 * ionode::GRAD_GC_WAVES) {
-    gerr("ionode_dopri5_backward_sse_gc: at most 65535 x 4 iterations per launch (HIP's grid.y limit): split the range"); return IONODE_ERR_ARG;
-  }
-  GArgs a = fill_args(d, d->mlp_layers, np_of(d->mlp_width), it_begin, it_end, n_iter, nullptr, prot_v, prot_t, prot_of_traj, t_eval, n_accepted,
-                      nullptr, nullptr, nullptr);
-  a.packets = packets; a.sse_y0 = sse_grad_y0;
-  a.grad_sse = grad_sse; a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
-  a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
-  return launch(sse_gc(d->state_f32), a, 0, stream);
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.prot_v = prot_v; b.prot_t = prot_t; b.prot_of_traj = prot_of_traj;
+  b.t_eval = t_eval; b.n_accepted = n_accepted; b.grad_sse = grad_sse; b.packets = packets; b.sse_grad_y0 = sse_grad_y0; b.stream = stream;
+  return checked_launch(SSE_GC, d, b);
 }
 
 int ionode_dopri5_backward_recompute_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
                                          const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                                          const double *t_eval, const int32_t *n_accepted, float *records, double *packets, void *stream) {
-  const int rc = sse_nn_check("ionode_dopri5_backward_recompute_sse", d, it_begin, it_end, n_iter);
-  if (rc != IONODE_OK) return rc;
-  return backward_impl(Sweep::Recompute, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, nullptr,
-                       nullptr, records, packets, nullptr, nullptr, stream, true, nullptr);
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.grad_image = grad_image; b.params = params; b.prot_v = prot_v;
+  b.prot_t = prot_t; b.prot_of_traj = prot_of_traj; b.t_eval = t_eval; b.n_accepted = n_accepted; b.records = records;
+  b.packets = packets; b.stream = stream;
+  return checked_launch(RECOMPUTE_SSE, d, b);
 }
 
 int ionode_dopri5_backward_sweep_sse(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
                                      const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                                      const double *t_eval, const int32_t *n_accepted, const double *sse_grad_y0, double *state,
                                      float *records, const double *packets, double *grad_params, double *grad_y0, void *stream) {
-  const int rc = sse_nn_check("ionode_dopri5_backward_sweep_sse", d, it_begin, it_end, n_iter);
-  if (rc != IONODE_OK) return rc;
-  return backward_impl(Sweep::Walk, d, it_begin, it_end, n_iter, grad_image, params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, nullptr,
-                       state, records, const_cast<double *>(packets), grad_params, grad_y0, stream, true, sse_grad_y0);
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.grad_image = grad_image; b.params = params; b.prot_v = prot_v;
+  b.prot_t = prot_t; b.prot_of_traj = prot_of_traj; b.t_eval = t_eval; b.n_accepted = n_accepted;
+  b.sse_grad_y0 = const_cast<double *>(sse_grad_y0); b.state = state; b.records = records; b.packets = const_cast<double *>(packets);
+  b.grad_params = grad_params; b.grad_y0 = grad_y0; b.stream = stream;
+  return checked_launch(SWEEP_SSE, d, b);
 }
 
 static int reduce_impl(int32_t L, int32_t N, const float *records, int64_t n_records, int32_t n_slabs, float *partials, void *stream,

@@ -43,7 +43,7 @@ void launch_sse_gc(const GArgs &a, unsigned, size_t, hipStream_t s) {
 }
 
 using SweepFn = void (*)(const GArgs &, unsigned grid, size_t lds, hipStream_t);
-enum class Sweep { OnePhase = 0, Recompute = 1, Walk = 2 };   // (the values are backward_impl's modes)
+enum class Sweep { OnePhase, Recompute, Walk, ClosedSse, SseGc };   // the launchers above, in their order
 
 // the launcher of an NN model's one-phase sweep or recompute kernel at width NT (the walk has no width: ionode_grad_capi.hip picks it)
 template <int MODEL, typename S, int NT> SweepFn pick_sweep(bool recompute) {

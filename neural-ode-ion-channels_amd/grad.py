@@ -21,6 +21,9 @@ sum_of_squares: the fused objective sse[b] = sum_k (i_k - ref_k)^2 with its grad
 models: the one-phase sweep with the seed formed in the kernel (ionode_dopri5_backward_sse).  NN models: the two-phase sweep above
 without grad_y -- ionode_dopri5_backward_sse_gc (csrc/ionode_grad_gc.hpp) forms each chunk's interpolant-coefficient adjoints and the
 sample-0 term, ionode_dopri5_backward_recompute_sse / _sweep_sse are the recompute and walk launches that take them.
+Both routes are one autograd Function each (_Solve, _SumOfSquares) over the same three pieces: _forward_with_checkpoints, _backward
+(failed trajectories masked, rows zeroed) and the chunk loop _sweep, which calls the seven sweep entry points through
+capi.sweep_launch with every buffer named (capi.SWEEP_BUFFERS).
 There is no CPU fallback: without libionode.so or a HIP device every call raises.
 """
 import ctypes as C
@@ -77,10 +80,25 @@ def stable_step_cap(model, params, prot_v, v_oob=-80.0, safety=3.0):
     return safety / lam_max if lam_max > 0 and np.isfinite(lam_max) else 0.0
 
 
-def _forward_with_checkpoints(launch, B, D, cfg, dev):
-    """Forward solve with accepted-step checkpoints: `launch(ckpt)` runs capi.dopri5 with the caller's keywords on a [B, cap, record]
-    buffer, which is sized by ckpt_cap / ckpt_budget_bytes and regrown (the forward runs again) until the steps of every trajectory that
-    SUCCEEDED fit.  Returns (result, ckpt, most accepted steps)."""
+def _forward_with_checkpoints(ctx, weights_flat, params, y0, cfg, objective):
+    """The forward of both autograd Functions: capi.dopri5 with the packed image of weights_flat (None: a closed-form model), cfg's
+    keywords and accepted-step checkpoints; objective: the fused sum of squares (sse_ref, obs_*; no state trace) instead of the states.
+    The [B, cap, record] checkpoint buffer is sized by ckpt_cap / ckpt_budget_bytes and regrown (the forward runs again) until the steps
+    of every trajectory that SUCCEEDED fit.  Saves what _backward reads on ctx and returns capi.dopri5's result."""
+    dev = y0.device
+    B, D = y0.shape
+    L, N = cfg["mlp_layers"], cfg["mlp_width"]
+    w_np, packed = None, None
+    if weights_flat is not None:
+        w_np = weights_flat.detach().to(torch.float32).cpu().numpy()
+        from . import batched  # packed forward image: shared cache with the plain solve
+        packed = batched.packed_weights(w_np, L, N, dev, key=cfg.get("weights_key"))
+    kw = dict(mlp_packed=packed, mlp_layers=L, mlp_width=N, prot_t=cfg.get("prot_t"), prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"],
+              prot_of_traj=cfg.get("prot_of_traj"), rtol=cfg["rtol"], atol=cfg["atol"], v_oob=cfg["v_oob"], max_steps=cfg["max_steps"],
+              max_total_steps=cfg["max_total_steps"], max_step=cfg.get("max_step", 0.0), tile_waves=cfg.get("tile_waves", 0),
+              t_eval_hint=cfg.get("t_eval_hint", "auto"))
+    if objective:
+        kw.update(obs_g=cfg["obs_g"], obs_e=cfg["obs_e"], obs_open_state_only=cfg["obs_open_state_only"], sse_ref=cfg["sse_ref"], states=False)
     cap = int(cfg.get("ckpt_cap") or DEFAULT_CKPT_CAP)
     limit = _bounded_budget(cfg.get("ckpt_budget_bytes"), DEFAULT_CKPT_BUDGET, dev, 0.6)
     row_bytes = B * capi.ckpt_record_doubles(D) * 8
@@ -89,14 +107,14 @@ def _forward_with_checkpoints(launch, B, D, cfg, dev):
     while True:
         ckpt = None   # (a regrown buffer replaces the old one instead of coexisting with it)
         ckpt = torch.empty((B, cap, capi.ckpt_record_doubles(D)), dtype=torch.float64, device=dev)
-        r = launch(ckpt)
+        r = capi.dopri5(cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], ckpt=ckpt, **kw)
         # the checkpoint buffer is sized for the trajectories that SUCCEEDED: a failed one (status != 0: step budget spent,
         # dt underflow) can have 10^5..10^6 accepted steps, contributes no gradient (its n_acc is zeroed in backward) and
         # must not grow a [B, cap, record] buffer to hundreds of GB
         nacc = torch.where(r["status"] == 0, r["stats"][:, 0], torch.zeros_like(r["stats"][:, 0]))
         most = int(nacc.max().item())
         if most <= cap:
-            return r, ckpt, most
+            break
         cap = 1 << int(np.ceil(np.log2(most + 1)))  # the buffer was too small: run the forward again with room
         if cap * row_bytes > limit and most * row_bytes <= limit:
             cap = limit // row_bytes   # the power of two does not fit the budget, the steps themselves do
@@ -104,10 +122,15 @@ def _forward_with_checkpoints(launch, B, D, cfg, dev):
         if need > limit:
             raise capi.IonodeError(f"checkpoints of {most} accepted steps x {B} trajectories need {need / 2**30:.1f} GiB "
                                    f"(> ckpt_budget_bytes = {limit / 2**30:.1f} GiB): split the batch or raise the budget")
+    ctx.cfg, ctx.desc, ctx.w_np = cfg, r["desc"], w_np
+    ctx.vtab = r["v_at_outputs"]   # (when the descriptor points at one, the backward reads V(t_k) from the same table)
+    ctx.save_for_backward(params.detach(), ckpt, r["stats"], r["status"])
+    ctx.mark_non_differentiable(r["status"])
+    return r
 
 
 def plan_backward_chunks(n_iter, tiles, record_floats, packet_doubles, budget, need_w, two_phase):
-    """How _Solve.backward cuts the n_iter sweep iterations into launches: (chunk, n_buf, bounds) -- iterations per chunk, buffer
+    """How _sweep cuts the n_iter sweep iterations into launches: (chunk, n_buf, bounds) -- iterations per chunk, buffer
     pairs (2: the next chunk is produced while this one is reduced / walked), and the chunks' [it0, it1) ranges.  Pure arithmetic
     (tests/test_host_logic.py replays tests/golden/grad_chunk_plans.json through it).
       with weight gradients   a chunk's record stream (6 records of record_floats fp32 per tile and iteration) fits the budget; once
@@ -185,69 +208,84 @@ def unpack_partial(part, L, N):
     return torch.cat(out)
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 class _Solve(torch.autograd.Function):
-    """y[B, Nt, 2] = dopri5 solve; differentiable in (weights_flat, params, y0)."""
+    """y[B, Nt, D] = dopri5 solve; differentiable in (weights_flat, params, y0)."""
 
     @staticmethod
     def forward(ctx, weights_flat, params, y0, cfg):
-        dev = y0.device
-        L, N = cfg["mlp_layers"], cfg["mlp_width"]
-        B = y0.shape[0]
-        w_np, packed = None, None
-        if weights_flat is not None:   # (None: the closed-form HH 2-state model)
-            w_np = weights_flat.detach().to(torch.float32).cpu().numpy()
-            from . import batched  # packed forward image: shared cache with the plain solve
-            packed = batched.packed_weights(w_np, L, N, dev, key=cfg.get("weights_key"))
-        r, ckpt, most = _forward_with_checkpoints(lambda ckpt: capi.dopri5(
-            cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], mlp_packed=packed,
-            mlp_layers=L, mlp_width=N, prot_t=cfg.get("prot_t"), prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"],
-            prot_of_traj=cfg.get("prot_of_traj"), rtol=cfg["rtol"], atol=cfg["atol"], v_oob=cfg["v_oob"],
-            max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"], max_step=cfg.get("max_step", 0.0), ckpt=ckpt,
-            tile_waves=cfg.get("tile_waves", 0), t_eval_hint=cfg.get("t_eval_hint", "auto")), B, y0.shape[1], cfg, dev)
-        ctx.cfg, ctx.desc = cfg, r["desc"]
-        ctx.w_np = w_np
-        ctx.save_for_backward(params.detach(), ckpt, r["stats"], r["status"])
-        ctx.mark_non_differentiable(r["status"])
-        ctx.n_acc_max = most
+        r = _forward_with_checkpoints(ctx, weights_flat, params, y0, cfg, objective=False)
         return r["y"], r["status"]
 
     @staticmethod
     def backward(ctx, gy, _gstatus):
-        cfg, desc = ctx.cfg, ctx.desc
-        params, ckpt, stats, status = ctx.saved_tensors
-        L, N = cfg["mlp_layers"], cfg["mlp_width"]
-        need_w = ctx.needs_input_grad[0] and ctx.w_np is not None
-        sdt = torch.float32 if desc.state_f32 else torch.float64
-        # failed trajectories (status != 0): their rows of y are NaN-filled and carry no gradient -- zero upstream rows (a caller's
-        # unmasked loss would otherwise feed NaN into the sweep) and, below, zero dL/dy0 / dL/dp rows
-        failed = status != 0
-        gy = torch.where(failed[:, None, None], torch.zeros((), dtype=gy.dtype, device=gy.device), gy).to(sdt).contiguous()
-        n_acc = torch.where(status == 0, stats[:, 0], torch.zeros_like(stats[:, 0])).to(torch.int32).contiguous()
-        acc, g_params, g_y0 = _sweep(cfg, desc, ctx.w_np, need_w, params, ckpt, n_acc, gy=gy)
-        g_params[failed] = 0.0
-        g_y0[failed] = 0.0
-        g_w = unpack_partial(acc, L, N).to(torch.float32) if need_w else None
-        return g_w, (g_params if ctx.needs_input_grad[1] else None), (g_y0.to(sdt) if ctx.needs_input_grad[2] else None), None
+        return _backward(ctx, gy, fused=False)
 
 
-def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, gy=None, g_sse=None):
-    """The backward sweep's chunk loop, shared by _Solve.backward (gy [B, Nt, D]: the upstream dL/dy in the state dtype) and
-    _SumOfSquaresNN.backward (g_sse [B] fp64: the upstream dL/dsse of the fused objective, NN models, two-phase only -- per chunk
-    ionode_dopri5_backward_sse_gc forms the packets' G_c on the phase-A stream and the products run without grad_y).  n_acc [B]
-    int32: accepted steps to replay (0 for failed trajectories).  Returns (padded partial weight gradient fp64 | None, dL/dp
-    [B, NPAR], dL/dy0 [B, D]), the rows of failed trajectories not yet zeroed."""
+class _SumOfSquares(torch.autograd.Function):
+    """sse[B] = sum_k (i_k - sse_ref[protocol][k])^2 of the fused forward; differentiable in (weights_flat, params, y0).  Nothing of size
+    [B, Nt] is ever allocated: the forward writes checkpoints and sse_out (no state trace), the backward sweeps with the [B] upstream
+    gradient."""
+
+    @staticmethod
+    def forward(ctx, weights_flat, params, y0, cfg):
+        r = _forward_with_checkpoints(ctx, weights_flat, params, y0, cfg, objective=True)
+        return r["sse"], r["status"]
+
+    @staticmethod
+    def backward(ctx, g_sse, _gstatus):
+        return _backward(ctx, g_sse, fused=True)
+
+
+def _backward(ctx, g, fused):
+    """The backward of both Functions: g is the upstream dL/dy [B, Nt, D], or (fused) dL/dsse [B].  Failed trajectories (status != 0:
+    their rows of y are NaN-filled, their sse is inf) carry no gradient: their upstream rows are zeroed (a caller's unmasked loss would
+    otherwise feed NaN into the sweep), they replay no steps, and their rows of dL/dp and dL/dy0 are zero."""
+    cfg, desc = ctx.cfg, ctx.desc
+    params, ckpt, stats, status = ctx.saved_tensors
+    sdt = torch.float32 if desc.state_f32 else torch.float64
+    failed = status != 0
+    g = torch.where(failed.reshape((-1,) + (1,) * (g.dim() - 1)), torch.zeros((), dtype=g.dtype, device=g.device), g)
+    g = g.to(torch.float64 if fused else sdt).contiguous()
+    n_acc = torch.where(failed, torch.zeros_like(stats[:, 0]), stats[:, 0]).to(torch.int32).contiguous()
+    need_w = ctx.needs_input_grad[0] and ctx.w_np is not None
+    acc, g_params, g_y0 = _sweep(cfg, desc, ctx.w_np, need_w, params, ckpt, n_acc, g, fused)
+    g_params[failed] = 0.0
+    g_y0[failed] = 0.0
+    g_w = unpack_partial(acc, cfg["mlp_layers"], cfg["mlp_width"]).to(torch.float32) if need_w else None
+    return g_w, (g_params if ctx.needs_input_grad[1] else None), (g_y0.to(sdt) if ctx.needs_input_grad[2] else None), None
+
+
+def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, g, fused):
+    """The backward sweep's chunk loop.  g: the upstream dL/dy [B, Nt, D] in the state dtype, or (fused) dL/dsse [B] fp64 of the
+    sum-of-squares objective -- closed-form models: one launch of ionode_dopri5_backward_sse; NN models: two-phase only, per chunk
+    ionode_dopri5_backward_sse_gc forms the packets' G_c on the phase-A stream and the products run without grad_y.  n_acc [B] int32:
+    accepted steps to replay (0 for failed trajectories).  Returns (padded partial weight gradient fp64 | None, dL/dp [B, NPAR], dL/dy0
+    [B, D]), the rows of failed trajectories not yet zeroed."""
     dev = params.device
     L, N = cfg["mlp_layers"], cfg["mlp_width"]
     B = desc.n_traj
     lib = capi.lib()
-    fused = g_sse is not None
+    # Two-phase sweep (NN models; csrc/ionode_grad.hpp, DESIGN.md 5.4).  A stage's vector-Jacobian product is linear in its seed
+    # (a scalar per trajectory) and everything else it needs comes from the step's checkpoint: phase A
+    # (ionode_dopri5_backward_recompute) computes the UNIT-SEED products of every (tile, step) of a chunk at once on the whole
+    # chip, on its own stream, one chunk AHEAD of phase B (ionode_dopri5_backward_sweep: the sequential walk, adjoint algebra
+    # only, one wavefront per tile); the reduction of a finished chunk (ionode_grad_reduce_unit: records scaled by the seeds
+    # the walk wrote) runs on a third stream.  Records and packets are double-buffered.
+    two_phase = bool(cfg.get("two_phase", os.environ.get("IONODE_GRAD_ONE_PHASE", "0") != "1")) and w_np is not None
+    if fused and w_np is not None and not two_phase:
+        raise capi.IonodeError("the fused sum-of-squares sweep of the NN models is two-phase only: use grad.solve for the one-phase sweep")
+    desc.ckpt, desc.ckpt_cap = ckpt.data_ptr(), ckpt.shape[1]
+    gc_desc = desc
+    if fused and two_phase and desc.v_at_outputs is None and 4 * desc.n_prot <= desc.n_traj:
+        # V(t_k) once per protocol ([P, Nt]) instead of one lookup per trajectory and sample: capi.dopri5's "auto" rule for the
+        # closed-form epilogue, here for the G_c launches alone (the NN forward has formed its own voltages already), which get a
+        # descriptor of their own that points at the table; it lives for this sweep
+        vtab = capi.protocol_at_outputs(desc, cfg["prot_v"], cfg.get("prot_t"), cfg["t_eval"])
+        gc_desc = capi.IonodeDesc.from_buffer_copy(desc)
+        gc_desc.v_at_outputs = vtab.data_ptr()
     n_iter = int(n_acc.max().item()) + 1
     image = grad_image(w_np, L, N, dev, key=cfg.get("weights_key")) if w_np is not None else None
-    D, npar = desc.n_state, (12 if desc.model == capi.MODEL_MARKOV6 else 8)
+    D, npar = desc.n_state, capi.n_params(desc.model)
     state = torch.empty((B, 2 * D + npar), dtype=torch.float64, device=dev)
     g_params = torch.zeros((B, npar), dtype=torch.float64, device=dev)
     g_y0 = torch.zeros((B, D), dtype=torch.float64, device=dev)
@@ -257,15 +295,6 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, gy=None, g_sse=None):
     budget = _bounded_budget(cfg.get("record_budget_bytes"), DEFAULT_RECORD_BUDGET, dev, 0.5)
     acc = torch.zeros(partf, dtype=torch.float64, device=dev) if need_w else None
     main = torch.cuda.current_stream(dev)
-    # Two-phase sweep (NN models; csrc/ionode_grad.hpp).  A stage's vector-Jacobian product is linear in its seed
-    # (a scalar per trajectory) and everything else it needs comes from the step's checkpoint: phase A
-    # (ionode_dopri5_backward_recompute) computes the UNIT-SEED products of every (tile, step) of a chunk at once on the whole
-    # chip, on its own stream, one chunk AHEAD of phase B (ionode_dopri5_backward_sweep: the sequential walk, adjoint algebra
-    # only, one wavefront per tile); the reduction of a finished chunk (ionode_grad_reduce_unit: records scaled by the seeds
-    # the walk wrote) runs on a third stream.  Records and packets are double-buffered.
-    two_phase = bool(cfg.get("two_phase", os.environ.get("IONODE_GRAD_ONE_PHASE", "0") != "1")) and image is not None
-    if fused and not two_phase:
-        raise capi.IonodeError("the fused sum-of-squares sweep of the NN models is two-phase only: use grad.solve for the one-phase sweep")
     pkd = int(lib.ionode_grad_packet_doubles()) if two_phase else 0
     chunk, n_buf, bounds = plan_backward_chunks(n_iter, tiles, recf, pkd, budget, need_w, two_phase)
     records = [torch.empty(tiles * chunk * 6 * recf, dtype=torch.float32, device=dev) for _ in range(n_buf)] if need_w else [None] * n_buf
@@ -273,13 +302,14 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, gy=None, g_sse=None):
     side = torch.cuda.Stream(dev) if (need_w and n_buf == 2) else main          # reductions
     pre = torch.cuda.Stream(dev) if (two_phase and n_buf == 2) else main         # phase A
     if pre is not main:
-        pre.wait_stream(main)    # gy (g_sse) / state / inputs were produced on the caller's stream
+        pre.wait_stream(main)    # g / state / inputs were produced on the caller's stream
     free = [None] * n_buf   # event: the reduce (or, without weight gradients, the walk) that last used this buffer pair has finished
     ready = [None] * n_buf  # event: phase A has filled this buffer pair
-    desc.ckpt, desc.ckpt_cap = ckpt.data_ptr(), ckpt.shape[1]
-    sse_y0 = torch.zeros((B, D), dtype=torch.float64, device=dev) if fused else None   # sample-0 term of dL/dy0: written by the last chunk's G_c launch
-    common = (_ptr(image), _ptr(params), _ptr(cfg["prot_v"]), _ptr(cfg.get("prot_t")), _ptr(cfg.get("prot_of_traj")),
-              _ptr(cfg["t_eval"]), _ptr(n_acc))
+    sse_y0 = torch.zeros((B, D), dtype=torch.float64, device=dev) if fused and two_phase else None   # sample-0 term of dL/dy0: written by the last chunk's G_c launch
+    # the entry points' buffers by name (capi.SWEEP_BUFFERS): what all seven take, what the launches that run the net add, the adjoint
+    shared = dict(prot_v=cfg["prot_v"], prot_t=cfg.get("prot_t"), prot_of_traj=cfg.get("prot_of_traj"), t_eval=cfg["t_eval"], n_accepted=n_acc)
+    net = dict(shared, grad_image=image, params=params)
+    adjoint = dict(state=state, grad_params=g_params, grad_y0=g_y0)
 
     def phase_a(k):
         it0, it1 = bounds[k]
@@ -287,17 +317,12 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, gy=None, g_sse=None):
         if free[b] is not None:
             pre.wait_event(free[b])
         if fused:   # G_c of the objective (one wavefront per trajectory and step), then the products without grad_y: same stream, same packets
-            rc = lib.ionode_dopri5_backward_sse_gc(C.byref(desc), it0, it1, n_iter, *common[2:], _ptr(g_sse), _ptr(packets[b]), _ptr(sse_y0),
-                                                   C.c_void_p(pre.cuda_stream))
-            if rc != 0:
-                raise capi.IonodeError(f"ionode_dopri5_backward_sse_gc failed ({rc}): {lib.ionode_grad_last_error().decode()}")
-            rc = lib.ionode_dopri5_backward_recompute_sse(C.byref(desc), it0, it1, n_iter, *common, _ptr(records[b]), _ptr(packets[b]),
-                                                          C.c_void_p(pre.cuda_stream))
+            capi.sweep_launch("ionode_dopri5_backward_sse_gc", gc_desc, it0, it1, n_iter, pre, grad_sse=g, packets=packets[b],
+                              sse_grad_y0=sse_y0, **shared)
+            capi.sweep_launch("ionode_dopri5_backward_recompute_sse", desc, it0, it1, n_iter, pre, records=records[b], packets=packets[b], **net)
         else:
-            rc = lib.ionode_dopri5_backward_recompute(C.byref(desc), it0, it1, n_iter, *common, _ptr(gy), _ptr(records[b]),
-                                                      _ptr(packets[b]), C.c_void_p(pre.cuda_stream))
-        if rc != 0:
-            raise capi.IonodeError(f"ionode_dopri5_backward_recompute failed ({rc}): {lib.ionode_grad_last_error().decode()}")
+            capi.sweep_launch("ionode_dopri5_backward_recompute", desc, it0, it1, n_iter, pre, grad_y=g, records=records[b],
+                              packets=packets[b], **net)
         ev = torch.cuda.Event()
         ev.record(pre)
         ready[b] = ev
@@ -311,16 +336,19 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, gy=None, g_sse=None):
             if k + 1 < len(bounds) and n_buf == 2:
                 phase_a(k + 1)                      # one chunk ahead, beside this chunk's walk
             main.wait_event(ready[b])
-            walk = lib.ionode_dopri5_backward_sweep_sse if fused else lib.ionode_dopri5_backward_sweep
-            rc = walk(C.byref(desc), it0, it1, n_iter, *common, _ptr(sse_y0 if fused else gy), _ptr(state), _ptr(rec),
-                      _ptr(packets[b]), _ptr(g_params), _ptr(g_y0), C.c_void_p(main.cuda_stream))
+            if fused:
+                capi.sweep_launch("ionode_dopri5_backward_sweep_sse", desc, it0, it1, n_iter, main, sse_grad_y0=sse_y0, records=rec,
+                                  packets=packets[b], **net, **adjoint)
+            else:
+                capi.sweep_launch("ionode_dopri5_backward_sweep", desc, it0, it1, n_iter, main, grad_y=g, records=rec, packets=packets[b],
+                                  **net, **adjoint)
         else:
             if free[b] is not None:
                 main.wait_event(free[b])
-            rc = lib.ionode_dopri5_backward(C.byref(desc), it0, it1, n_iter, *common, _ptr(gy), _ptr(state), _ptr(rec),
-                                            _ptr(g_params), _ptr(g_y0), C.c_void_p(main.cuda_stream))
-        if rc != 0:
-            raise capi.IonodeError(f"backward sweep failed ({rc}): {lib.ionode_grad_last_error().decode()}")
+            if fused:   # closed-form models: the seed is formed in the kernel; one launch (plan_backward_chunks: nothing to buffer)
+                capi.sweep_launch("ionode_dopri5_backward_sse", desc, it0, it1, n_iter, main, params=params, grad_sse=g, **shared, **adjoint)
+            else:
+                capi.sweep_launch("ionode_dopri5_backward", desc, it0, it1, n_iter, main, grad_y=g, records=rec, **net, **adjoint)
         swept = torch.cuda.Event()
         swept.record(main)
         if need_w:
@@ -330,7 +358,7 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, gy=None, g_sse=None):
             with torch.cuda.stream(side):
                 partials = torch.empty((n_slabs, partf), dtype=torch.float32, device=dev)
                 reduce = lib.ionode_grad_reduce_unit if two_phase else lib.ionode_grad_reduce   # unit-seed records: scaled while staged
-                rc = reduce(L, N, _ptr(rec), n_rec, n_slabs, _ptr(partials), C.c_void_p(side.cuda_stream))
+                rc = reduce(L, N, C.c_void_p(rec.data_ptr()), n_rec, n_slabs, C.c_void_p(partials.data_ptr()), C.c_void_p(side.cuda_stream))
                 if rc != 0:
                     raise capi.IonodeError(f"ionode_grad_reduce failed ({rc}): {lib.ionode_grad_last_error().decode()}")
                 acc += partials.double().sum(0)
@@ -415,118 +443,11 @@ def allreduce_gradients(tensors, group=None):
     return out
 
 
-class _SumOfSquares(torch.autograd.Function):
-    """sse[B] = sum_k (i_k - sse_ref[protocol][k])^2 of the fused forward; differentiable in (params, y0).  Nothing of size
-    [B, Nt] is ever allocated: forward ionode_dopri5 with checkpoints and sse_out (no state trace), backward
-    ionode_dopri5_backward_sse with the [B] upstream gradient."""
-
-    @staticmethod
-    def forward(ctx, params, y0, cfg):
-        dev = y0.device
-        B, D = y0.shape
-        r, ckpt, _most = _forward_with_checkpoints(lambda ckpt: capi.dopri5(
-            cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], prot_t=cfg["prot_t"],
-            prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"], prot_of_traj=cfg["prot_of_traj"], rtol=cfg["rtol"],
-            atol=cfg["atol"], v_oob=cfg["v_oob"], max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"],
-            max_step=cfg["max_step"], ckpt=ckpt, obs_g=cfg["obs_g"], obs_e=cfg["obs_e"],
-            obs_open_state_only=cfg["obs_open_state_only"], t_eval_hint=cfg["t_eval_hint"],
-            sse_ref=cfg["sse_ref"], states=False), B, D, cfg, dev)
-        ctx.cfg, ctx.desc = cfg, r["desc"]
-        ctx.vtab = r["v_at_outputs"]   # the descriptor points at it: the backward reads V(t_k) from the same table
-        ctx.sdt = y0.dtype
-        ctx.save_for_backward(params.detach(), ckpt, r["stats"], r["status"])
-        ctx.mark_non_differentiable(r["status"])
-        return r["sse"], r["status"]
-
-    @staticmethod
-    def backward(ctx, g_sse, _gstatus):
-        cfg, desc = ctx.cfg, ctx.desc
-        params, ckpt, stats, status = ctx.saved_tensors
-        dev = params.device
-        B, D = desc.n_traj, desc.n_state
-        npar = 12 if desc.model == capi.MODEL_MARKOV6 else 8
-        failed = status != 0
-        # failed trajectories (sse = inf): their upstream rows are ignored and their gradient rows are zero
-        g = torch.where(failed, torch.zeros((), dtype=torch.float64, device=dev), g_sse.to(torch.float64)).contiguous()
-        n_acc = torch.where(failed, torch.zeros_like(stats[:, 0]), stats[:, 0]).to(torch.int32).contiguous()
-        n_iter = int(n_acc.max().item()) + 1
-        state = torch.empty((B, 2 * D + npar), dtype=torch.float64, device=dev)
-        g_params = torch.zeros((B, npar), dtype=torch.float64, device=dev)
-        g_y0 = torch.zeros((B, D), dtype=torch.float64, device=dev)
-        desc.ckpt, desc.ckpt_cap = ckpt.data_ptr(), ckpt.shape[1]
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        rc = capi.lib().ionode_dopri5_backward_sse(C.byref(desc), 0, n_iter, n_iter, _ptr(params), _ptr(cfg["prot_v"]),
-                                                   _ptr(cfg["prot_t"]), _ptr(cfg["prot_of_traj"]), _ptr(cfg["t_eval"]), _ptr(n_acc),
-                                                   _ptr(g), _ptr(state), _ptr(g_params), _ptr(g_y0), stream)
-        if rc != 0:
-            raise capi.IonodeError(f"ionode_dopri5_backward_sse failed ({rc}): {capi.lib().ionode_grad_last_error().decode()}")
-        g_params[failed] = 0.0
-        g_y0[failed] = 0.0
-        return (g_params if ctx.needs_input_grad[0] else None), (g_y0.to(ctx.sdt) if ctx.needs_input_grad[1] else None), None
-
-
-class _SumOfSquaresNN(torch.autograd.Function):
-    """sse[B] of the fused forward for NN-f / NN-d; differentiable in (weights_flat, params, y0).  Forward: ionode_dopri5 with
-    checkpoints, sse_out and the packed weights, no state trace.  Backward: _Solve.backward's two-phase chunk loop (_sweep) with the
-    [B] upstream gradient -- ionode_dopri5_backward_sse_gc forms each chunk's G_c, the products run without grad_y."""
-
-    @staticmethod
-    def forward(ctx, weights_flat, params, y0, cfg):
-        dev = y0.device
-        B, D = y0.shape
-        L, N = cfg["mlp_layers"], cfg["mlp_width"]
-        w_np = weights_flat.detach().to(torch.float32).cpu().numpy()
-        from . import batched  # packed forward image: shared cache with the plain solve
-        packed = batched.packed_weights(w_np, L, N, dev, key=cfg.get("weights_key"))
-        r, ckpt, _most = _forward_with_checkpoints(lambda ckpt: capi.dopri5(
-            cfg["model"], params.detach(), cfg["prot_v"], y0.detach(), cfg["t_eval"], mlp_packed=packed, mlp_layers=L, mlp_width=N,
-            prot_t=cfg["prot_t"], prot_t0=cfg["prot_t0"], prot_dt=cfg["prot_dt"], prot_of_traj=cfg["prot_of_traj"], rtol=cfg["rtol"],
-            atol=cfg["atol"], v_oob=cfg["v_oob"], max_steps=cfg["max_steps"], max_total_steps=cfg["max_total_steps"],
-            max_step=cfg["max_step"], ckpt=ckpt, obs_g=cfg["obs_g"], obs_e=cfg["obs_e"],
-            obs_open_state_only=cfg["obs_open_state_only"], t_eval_hint=cfg["t_eval_hint"],
-            sse_ref=cfg["sse_ref"], states=False), B, D, cfg, dev)
-        ctx.cfg, ctx.desc = cfg, r["desc"]
-        ctx.vtab = r["v_at_outputs"]   # (when the descriptor points at one, the backward reads V(t_k) from the same table)
-        ctx.w_np, ctx.sdt = w_np, y0.dtype
-        ctx.save_for_backward(params.detach(), ckpt, r["stats"], r["status"])
-        ctx.mark_non_differentiable(r["status"])
-        return r["sse"], r["status"]
-
-    @staticmethod
-    def backward(ctx, g_sse, _gstatus):
-        cfg, desc = ctx.cfg, ctx.desc
-        params, ckpt, stats, status = ctx.saved_tensors
-        failed = status != 0
-        # failed trajectories (sse = inf): their upstream rows are ignored and their gradient rows are zero
-        g = torch.where(failed, torch.zeros((), dtype=torch.float64, device=params.device), g_sse.to(torch.float64)).contiguous()
-        n_acc = torch.where(failed, torch.zeros_like(stats[:, 0]), stats[:, 0]).to(torch.int32).contiguous()
-        need_w = ctx.needs_input_grad[0]
-        vtab = None
-        if desc.v_at_outputs is None and 4 * desc.n_prot <= desc.n_traj:
-            # V(t_k) once per protocol ([P, Nt]) instead of one lookup per trajectory and sample: capi.dopri5's "auto" rule for the
-            # closed-form epilogue, here for the G_c kernel alone (the NN forward has formed its own voltages already)
-            vtab = capi.protocol_at_outputs(desc, cfg["prot_v"], cfg["prot_t"], cfg["t_eval"])
-            desc.v_at_outputs = vtab.data_ptr()
-        acc, g_params, g_y0 = _sweep(cfg, desc, ctx.w_np, need_w, params, ckpt, n_acc, g_sse=g)
-        g_params[failed] = 0.0
-        g_y0[failed] = 0.0
-        if vtab is not None:
-            desc.v_at_outputs = None   # (the table lives for this backward only)
-        g_w = unpack_partial(acc, cfg["mlp_layers"], cfg["mlp_width"]).to(torch.float32) if need_w else None
-        return g_w, (g_params if ctx.needs_input_grad[1] else None), (g_y0.to(ctx.sdt) if ctx.needs_input_grad[2] else None), None
-
-
 def uniform_grid_hint(t_eval):
     """(t0, dt) of a uniform output grid -- what the fused objective's output cursor needs (ionode_desc.t_eval_dt_hint; the
-    kernel verifies it against t_eval) -- or None: capi.dopri5's "auto" rule (every t_k within dt / 2 of t0 + k dt)."""
-    n = int(t_eval.shape[0])
-    if n < 2:
-        return None
-    t0 = t_eval[0]
-    dt = (t_eval[n - 1] - t0) / (n - 1)
-    dev = (t_eval - (t0 + torch.arange(n, dtype=torch.float64, device=t_eval.device) * dt)).abs().max()
-    v = torch.stack([t0, dt, dev]).cpu()
-    return (float(v[0]), float(v[1])) if float(v[1]) > 0 and float(v[2]) <= 0.5 * float(v[1]) else None
+    kernel verifies it against t_eval) -- or None: capi.dopri5's "auto" rule (capi.uniform_grid: every t_k within dt / 2 of t0 + k dt)."""
+    grid = capi.uniform_grid(t_eval)
+    return None if grid is None else grid[:2]
 
 
 def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, prot_t0=0.0, prot_dt=1.0, prot_of_traj=None,
@@ -570,9 +491,9 @@ def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, p
     max_step = _resolve_max_step(model, params, prot_v, v_oob, max_step)
     if not (isinstance(y0, torch.Tensor) and y0.is_cuda):
         raise capi.IonodeError("no HIP tensors: the integrator and its backward sweep have no CPU path")
-    D = 6 if model == capi.MODEL_MARKOV6 else 2
+    D = capi.n_state(model)
     if y0.dim() != 2 or y0.shape[1] != D or params.dim() != 2 or params.shape[0] != y0.shape[0]:
-        raise capi.IonodeError(f"params [B, {12 if D == 6 else 8}] and y0 [B, {D}] expected")
+        raise capi.IonodeError(f"params [B, {capi.n_params(model)}] and y0 [B, {D}] expected")
     hint = uniform_grid_hint(t_eval)
     if hint is None:
         raise capi.IonodeError("grad.sum_of_squares needs a uniform output grid t_eval (the fused objective's output cursor); for "
@@ -581,9 +502,7 @@ def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, p
                prot_of_traj=None if prot_of_traj is None else torch.as_tensor(prot_of_traj, device=y0.device).to(torch.int32).contiguous(),
                rtol=float(rtol), atol=float(atol), v_oob=float(v_oob), max_steps=int(max_steps), max_total_steps=int(max_total_steps),
                max_step=float(max_step), obs_g=float(obs_g), obs_e=float(obs_e), obs_open_state_only=bool(obs_open_state_only),
-               t_eval_hint=hint, sse_ref=sse_ref, ckpt_cap=ckpt_cap, ckpt_budget_bytes=ckpt_budget_bytes)
-    if nn:
-        cfg.update(mlp_layers=int(mlp_layers), mlp_width=int(mlp_width), weights_key=weights_key, record_budget_bytes=record_budget_bytes,
-                   two_phase=True)
-        return _SumOfSquaresNN.apply(weights_flat, params, y0.contiguous(), cfg)
-    return _SumOfSquares.apply(params, y0.contiguous(), cfg)
+               t_eval_hint=hint, sse_ref=sse_ref, ckpt_cap=ckpt_cap, ckpt_budget_bytes=ckpt_budget_bytes,
+               mlp_layers=int(mlp_layers) if nn else 0, mlp_width=int(mlp_width) if nn else 0, weights_key=weights_key,
+               record_budget_bytes=record_budget_bytes, two_phase=True)
+    return _SumOfSquares.apply(weights_flat, params, y0.contiguous(), cfg)
