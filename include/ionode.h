@@ -299,11 +299,18 @@ int ionode_dopri5_backward_sweep_sse(const ionode_desc *d, int32_t it_begin, int
 size_t ionode_grad_partial_floats(int32_t mlp_layers, int32_t mlp_width);
 
 /* The slab count that makes one round of workgroups of ionode_grad_reduce() on the current device (256 compute units when there is
- * none): a slab costs mlp_layers x (column blocks of the width) heavy workgroups + one light one, N = 200 runs two workgroups per
- * compute unit.  Any n_slabs >= 1 is valid; this one is the fastest.  Since ABI 9. */
+ * none): a slab costs mlp_layers x (column blocks of the width) heavy workgroups + one light one, N = 200 runs three workgroups per
+ * compute unit.  It is the plan of the kernel that will run for the width: a width without a tuned reduce kernel (N does not pad to
+ * 16, 112, 208 or 512), or any width under IONODE_GRAD_GENERIC=1, gets the run-time-width kernel's -- mlp_layers x
+ * ceil(NT / 8) x ceil(NT / 16) heavy workgroups + one light one per slab (NT = ceil(N / 16)), two workgroups per compute unit.
+ * Any n_slabs >= 1 is valid; this one is the fastest.  Since ABI 9. */
 int32_t ionode_grad_reduce_slabs(int32_t mlp_layers, int32_t mlp_width, int64_t n_records);
 
-/* partials[n_slabs][ionode_grad_partial_floats()] = per-slab sums over records [n_records * s / n_slabs, ...); asynchronous */
+/* partials[n_slabs][ionode_grad_partial_floats()] = per-slab sums over records [n_records * s / n_slabs, ...); asynchronous.
+ * Every 1 <= N <= 512 at any depth: the tuned kernel where N pads to 16, 112, 208 or 512, the run-time-width kernel
+ * otherwise (same records, same partial layout, every element one chain over the slab's records in record order).
+ * IONODE_GRAD_GENERIC=1 in the environment (read on every call; a development switch) sends every width, and
+ * ionode_grad_reduce_unit() with it, to the run-time-width kernel. */
 int ionode_grad_reduce(int32_t mlp_layers, int32_t mlp_width, const float *records, int64_t n_records, int32_t n_slabs,
                        float *partials, void *stream);
 
@@ -316,10 +323,21 @@ int ionode_grad_reduce(int32_t mlp_layers, int32_t mlp_width, const float *recor
 
 /* Forward + backward of the net for every 16-row tile of x (fp32 MFMA, activations LDS-resident): one record per tile into
  * `records` ([ceil(n_rows/16)][ionode_grad_record_floats()]) and sum((p - y)^2) partials into loss_partials[n_workgroups]
- * (fp64).  x [n_rows][2], y [n_rows], offset [n_rows] or NULL: device fp32.  n_workgroups = persistent grid size (<= tiles). */
+ * (fp64).  x [n_rows][2], y [n_rows], offset [n_rows] or NULL: device fp32.  n_workgroups = persistent grid size (<= tiles).
+ * Served shapes: 1..15 hidden layers, 1 <= N <= 512, and the tile's LDS (ionode_regress_plan) within a compute unit's 160 KiB.
+ * N that pads to 16, 112, 208 or 512 runs its tuned kernel (N = 497..512: up to 10 layers); every other width runs the run-time-width
+ * kernel (same arithmetic order, records bit-identical where both exist): all of 1..15 layers up to N = 416 and for N = 433..448, up to
+ * 10 layers for N = 417..432, up to 14 for N = 449..464, up to 7 for N = 465..480, and none for N = 481..496 (IONODE_ERR_UNSUPPORTED, the message names the LDS need).
+ * IONODE_GRAD_GENERIC=1 (read on every call; a development switch) sends every width to the run-time-width kernel. */
 int ionode_regress_step(int32_t mlp_layers, int32_t mlp_width, const float *grad_image, const float *x, const float *offset,
                         const float *y, int32_t n_rows, float netscale, float *records, double *loss_partials,
                         int32_t n_workgroups, void *stream);
+
+/* Pure host code (no HIP call; ABI 10, new symbol): the plan of ionode_regress_step() at (mlp_layers, mlp_width).
+ * out = {1 if the run-time-width kernel serves the shape, 0 if a tuned one does; workgroups of the kernel per compute unit (the
+ * persistent grid's size is that times the device's compute units, at most the tile count); LDS bytes per workgroup}.
+ * IONODE_ERR_UNSUPPORTED with ionode_grad_last_error() set when nothing serves the shape. */
+int ionode_regress_plan(int32_t mlp_layers, int32_t mlp_width, int32_t out[3]);
 
 /* g[i] = sum over slabs of partials[s][padmap[i]] (flat state-dict order), then torch.optim.Adam's update (no amsgrad, no
  * weight decay), element-wise in fp32.  `step` counts from 1.  grad_out (optional) receives g; apply = 0 only gathers g. */

@@ -30,7 +30,7 @@ EXPORTS = (
     "ionode_grad_packet_doubles", "ionode_dopri5_backward_recompute", "ionode_dopri5_backward_sweep",
     "ionode_dopri5_backward_sse_gc", "ionode_dopri5_backward_recompute_sse", "ionode_dopri5_backward_sweep_sse",
     "ionode_grad_partial_floats", "ionode_grad_reduce", "ionode_grad_reduce_unit", "ionode_grad_reduce_slabs", "ionode_grad_last_error",
-    "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh",
+    "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh", "ionode_regress_plan",
 )
 
 # the backward sweep's entry points: their buffers in ABI order -- between (d, it_begin, it_end, n_iter) and stream (include/ionode.h;
@@ -136,6 +136,8 @@ def lib():
         L.ionode_regress_step.restype = C.c_int
         L.ionode_regress_step.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                           C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
+        L.ionode_regress_plan.restype = C.c_int
+        L.ionode_regress_plan.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 3)]
         L.ionode_adam_step.restype = C.c_int
         L.ionode_adam_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
@@ -195,6 +197,15 @@ def launch_geometry(desc):
     if rc != 0:
         raise IonodeError(last_error())
     return {"grid": out[0], "block": out[1], "lds_bytes": out[2], "tile_waves": out[3]}
+
+
+def regress_plan(mlp_layers, mlp_width):
+    """Plan of the regression step at (L, N), pure host code (ionode_regress_plan): which kernel serves it, its workgroups per compute
+    unit and its LDS.  Raises IonodeError with the library's message for a shape nothing serves."""
+    out = (C.c_int32 * 3)()
+    if lib().ionode_regress_plan(int(mlp_layers), int(mlp_width), C.byref(out)) != 0:
+        raise IonodeError(lib().ionode_grad_last_error().decode())
+    return {"generic": bool(out[0]), "wg_per_cu": out[1], "lds_bytes": out[2]}
 
 
 def kernel_name(desc):

@@ -6,6 +6,7 @@
 
 #include "ionode_grad_launch.hpp"
 #include "ionode_grad_reduce.hpp"
+#include "ionode_grad_gen_plan.hpp"
 
 namespace {
 
@@ -318,9 +319,12 @@ int ionode_dopri5_backward_sweep_sse(const ionode_desc *d, int32_t it_begin, int
 static int reduce_impl(int32_t L, int32_t N, const float *records, int64_t n_records, int32_t n_slabs, float *partials, void *stream,
                        int unit_seed) {
   if (!records || !partials || n_records < 1 || n_slabs < 1 || L < 1 || N < 1) { gerr("ionode_grad_reduce: bad argument"); return IONODE_ERR_ARG; }
+  if (N > 512) return refuse(IONODE_ERR_UNSUPPORTED, "ionode_grad_reduce: width outside the served shapes (N <= 512)");   // (no depth limit: the kernels have none)
   const int NT = np_of(N) / 16;
-  const hipError_t e = ionode::launch_grad_reduce(L, NT, records, n_records, n_slabs, partials, reinterpret_cast<hipStream_t>(stream), unit_seed);
-  if (e == hipErrorInvalidValue) { gerr("ionode_grad_reduce: width outside the compiled variants"); return IONODE_ERR_UNSUPPORTED; }
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  // the tuned instantiation where for_width has one, the run-time-width kernel (inst_grad_gen.hip) otherwise or when forced
+  const hipError_t e = ionode::grad_use_gen(NT) ? ionode::launch_grad_reduce_gen(L, NT, records, n_records, n_slabs, partials, s, unit_seed)
+                                                : ionode::launch_grad_reduce(L, NT, records, n_records, n_slabs, partials, s, unit_seed);
   if (e != hipSuccess) { gerr(hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
   return IONODE_OK;
 }
@@ -332,7 +336,8 @@ int32_t ionode_grad_reduce_slabs(int32_t L, int32_t N, int64_t n_records) {
     (void)hipGetLastError();
     cus = 256;   // (no device: the plan of an unpartitioned MI355X)
   }
-  return ionode::grad_reduce_slabs(L, np_of(N) / 16, cus, n_records);
+  const int NT = np_of(N) / 16;   // (the plan of the kernel that reduce_impl will launch for this width)
+  return ionode::grad_use_gen(NT) ? ionode::grad_gen_reduce_slabs(L, NT, cus, n_records) : ionode::grad_reduce_slabs(L, NT, cus, n_records);
 }
 
 int ionode_grad_reduce(int32_t L, int32_t N, const float *records, int64_t n_records, int32_t n_slabs, float *partials,
@@ -345,23 +350,40 @@ int ionode_grad_reduce_unit(int32_t L, int32_t N, const float *records, int64_t 
   return reduce_impl(L, N, records, n_records, n_slabs, partials, stream, 1);
 }
 
+// Pure host: which kernel serves the regression step at (L, N), its workgroups per compute unit and its LDS.  No HIP call in here.
+int ionode_regress_plan(int32_t L, int32_t N, int32_t out[3]) {
+  if (!out) { gerr("ionode_regress_plan: bad argument"); return IONODE_ERR_ARG; }
+  if (L < 1 || L > ionode::GRAD_MAX_LAYERS || N < 1 || N > 512)
+    return refuse(IONODE_ERR_UNSUPPORTED, "ionode_regress_step: (L = %d, N = %d) outside the served shapes (1 <= N <= 512, 1 to 15 hidden layers)", (int)L, (int)N);
+  const int NT = np_of(N) / 16;
+  const bool gen = ionode::grad_use_gen(NT);
+  const size_t lds = gen ? ionode::grad_gen_lds_bytes(L, NT) : ionode::grad_lds_bytes(L, NT);
+  if (lds > ionode::GRAD_LDS_LIMIT)
+    return refuse(IONODE_ERR_UNSUPPORTED, "ionode_regress_step: (L = %d, N = %d) needs %zu bytes of LDS per workgroup, a compute unit has %zu", (int)L, (int)N,
+                  lds, ionode::GRAD_LDS_LIMIT);
+  out[0] = gen ? 1 : 0;
+  out[1] = gen ? ionode::grad_gen_wg_per_cu(L, NT) : (NT <= 13 ? IONODE_REGRESS_WG_PER_CU : 1);
+  out[2] = (int32_t)lds;
+  return IONODE_OK;
+}
+
 int ionode_regress_step(int32_t L, int32_t N, const float *grad_image, const float *x, const float *offset, const float *y,
                         int32_t n_rows, float netscale, float *records, double *loss_partials, int32_t n_workgroups,
                         void *stream) {
   if (!grad_image || !x || !y || !records || !loss_partials || n_rows < 1 || n_workgroups < 1 || L < 1 || N < 1) {
     gerr("ionode_regress_step: bad argument"); return IONODE_ERR_ARG;
   }
+  int32_t plan[3];
+  if (const int rc = ionode_regress_plan(L, N, plan)) return rc;   // (refusals: its message)
   const int NT = np_of(N) / 16;
-  if (ionode::grad_lds_bytes(L, NT) > 160 * 1024 || L > 15) { gerr("ionode_regress_step: (L, N) outside the compiled variants (at most 15 hidden layers)"); return IONODE_ERR_UNSUPPORTED; }
   ionode::RArgs a;
   memset(&a, 0, sizeof a);
   a.img = grad_image; a.x = x; a.y = y; a.offset = offset; a.records = records; a.loss_part = loss_partials;
   a.M = n_rows; a.L = L; a.N = N; a.NT = NT; a.record_floats = ionode::grad_record_floats(L, NT); a.netscale = netscale;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (!ionode::for_width(NT, [&](auto nt) { ionode::launch_regress<decltype(nt)::value>(a, (unsigned)n_workgroups, s); },
-                         [&] { ionode::launch_regress32(a, (unsigned)n_workgroups, s); })) {
-    gerr("ionode_regress_step: width outside the compiled variants (N pads to 16, 112, 208 or 512)"); return IONODE_ERR_UNSUPPORTED;
-  }
+  if (plan[0]) ionode::launch_regress_gen(a, (unsigned)n_workgroups, s);   // inst_grad_gen.hip
+  else ionode::for_width(NT, [&](auto nt) { ionode::launch_regress<decltype(nt)::value>(a, (unsigned)n_workgroups, s); },
+                         [&] { ionode::launch_regress32(a, (unsigned)n_workgroups, s); });
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) { gerr(hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
   return IONODE_OK;

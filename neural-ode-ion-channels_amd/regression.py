@@ -35,6 +35,7 @@ class MlpRegression:
         self.L, self.N = int(mlp_layers), int(mlp_width)
         L, N, dev = self.L, self.N, self.dev
         lib = capi.lib()
+        plan = capi.regress_plan(L, N)   # (raises the library's message for a shape no kernel serves, before anything is allocated)
         n = 2 * N + N + L * (N * N + N) + N + 1
         w = np.ascontiguousarray(np.asarray(weights_flat, dtype=np.float32).reshape(-1))
         if w.size != n:
@@ -63,9 +64,10 @@ class MlpRegression:
         self.recf = lib.ionode_grad_record_floats(L, N)
         self.records = torch.empty(self.tiles * self.recf, dtype=torch.float32, device=dev)
         cus = torch.cuda.get_device_properties(dev).multi_processor_count
-        # persistent grid: TWO workgroups per compute unit for N <= 200 (256 registers and 70 KB of LDS each: one tile's layer boundaries
-        # run beside the other's MFMAs), one for N = 500.  IONODE_REGRESS_WG_PER_CU: dev override for A/B runs
-        per_cu = int(os.environ.get("IONODE_REGRESS_WG_PER_CU", "2" if N <= 208 else "1"))
+        # persistent grid: the workgroups per compute unit of the kernel that serves (L, N), from the library -- the tuned kernels: TWO for
+        # N <= 200 (256 registers and 70 KB of LDS each: one tile's layer boundaries run beside the other's MFMAs), one for N = 500; the
+        # run-time-width kernel: what its LDS lets in, at most four.  IONODE_REGRESS_WG_PER_CU: dev override for A/B runs
+        per_cu = int(os.environ.get("IONODE_REGRESS_WG_PER_CU", plan["wg_per_cu"]))
         self.n_wg = int(min(self.tiles, cus * per_cu))
         self.n_slabs = int(os.environ.get("IONODE_REGRESS_SLABS", 0)) or int(lib.ionode_grad_reduce_slabs(L, N, self.tiles))   # (one round of the reduce kernel's workgroups on this device; env: dev override for A/B runs)
         self.loss_part = torch.zeros(self.n_wg, dtype=torch.float64, device=dev)
