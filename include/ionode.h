@@ -159,6 +159,32 @@ int ionode_dopri5(const ionode_desc *d, const float *mlp_packed, const double *p
                   const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
                   void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream);
 
+/*
+ * Deferred dense output (since ABI 10, added later: new symbols only, ionode_desc and every earlier entry point unchanged).
+ * The lean N = 200 16-trajectory tile kernels (NN-f / NN-d, both state dtypes: verified uniform output grid, uniform protocol grid,
+ * no step log, no checkpoints) can leave the dense output of their accepted steps to a second, store-bound kernel: a step writes one
+ * 112-byte record (t0, step length, its reciprocal, first output index and output count, the 5 x 2 interpolant coefficients) into a
+ * caller-owned workspace, and ionode_dense_expand_kernel evaluates and stores the samples after the solve, on the same stream.
+ * y_out, i_out, status and stats are bit for bit those of ionode_dopri5().
+ *
+ * ionode_dense_defer_plan(): pure host code.  out = {records per trajectory, workspace bytes} for `d` (want_current: an i_out buffer
+ * will be passed), both 0 when nothing would be deferred -- another kernel variant, the fused objective (sse_out), or
+ * IONODE_DEFER_DENSE=0 in the environment.  The records may take a quarter of the bytes of the requested outputs:
+ * capacity = min(n_out - 1, that / (n_traj * 112)), and a capacity under 64 defers nothing.  A trajectory that fills its records
+ * emits its later steps itself, as without the workspace.  IONODE_DEFER_DENSE_CAP=n forces a capacity (both are development
+ * switches, read per plan).  Workspace layout: int32 count per trajectory, then (16-byte aligned) records [n_traj][capacity][14] fp64,
+ * indexed by trajectory whatever the launch order.
+ *
+ * ionode_dopri5_deferred(): ionode_dopri5() plus `workspace` (DEVICE, 16-byte aligned, at least the plan's bytes, contents
+ * undefined before and after) and its size.  workspace == NULL, or a descriptor whose plan defers nothing (an explicit prot_t
+ * included), is exactly ionode_dopri5(); IONODE_ERR_ARG for a workspace smaller than the plan's.
+ */
+int ionode_dense_defer_plan(const ionode_desc *d, int32_t want_current, int64_t out[2]);
+int ionode_dopri5_deferred(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
+                           const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
+                           void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace,
+                           int64_t workspace_bytes);
+
 /* Pre-pass for ionode_desc.v_at_outputs: v_out[p][k] = V_p(t_eval[k]) for the d->n_prot protocols at the d->n_out output
  * times, by the integrator's own lookup (linear interpolation, -80 mV / v_oob outside the protocol: train-s1.py:218-237).
  * Reads d->n_out, n_prot, prot_n, prot_t0, prot_dt, v_oob.  Asynchronous on `stream`. */

@@ -31,6 +31,7 @@ EXPORTS = (
     "ionode_dopri5_backward_sse_gc", "ionode_dopri5_backward_recompute_sse", "ionode_dopri5_backward_sweep_sse",
     "ionode_grad_partial_floats", "ionode_grad_reduce", "ionode_grad_reduce_unit", "ionode_grad_reduce_slabs", "ionode_grad_last_error",
     "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh", "ionode_regress_plan",
+    "ionode_dense_defer_plan", "ionode_dopri5_deferred",
 )
 
 # the backward sweep's entry points: their buffers in ABI order -- between (d, it_begin, it_end, n_iter) and stream (include/ionode.h;
@@ -116,6 +117,10 @@ def lib():
         L.ionode_launch_geometry.argtypes = [C.POINTER(IonodeDesc), C.POINTER(C.c_int32 * 4)]
         L.ionode_dopri5.restype = C.c_int
         L.ionode_dopri5.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 12
+        L.ionode_dopri5_deferred.restype = C.c_int
+        L.ionode_dopri5_deferred.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 13 + [C.c_int64]
+        L.ionode_dense_defer_plan.restype = C.c_int
+        L.ionode_dense_defer_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int64 * 2)]
         L.ionode_grad_last_error.restype = C.c_char_p
         for fn in (L.ionode_grad_image_floats, L.ionode_grad_record_floats, L.ionode_grad_partial_floats):
             fn.restype = C.c_size_t
@@ -206,6 +211,15 @@ def regress_plan(mlp_layers, mlp_width):
     if lib().ionode_regress_plan(int(mlp_layers), int(mlp_width), C.byref(out)) != 0:
         raise IonodeError(lib().ionode_grad_last_error().decode())
     return {"generic": bool(out[0]), "wg_per_cu": out[1], "lds_bytes": out[2]}
+
+
+def dense_defer_plan(desc, want_current):
+    """Deferred dense output of the lean N = 200 16-tile (ionode_dense_defer_plan, pure host code): records per trajectory and
+    workspace bytes ionode_dopri5_deferred wants for `desc`; capacity 0: nothing is deferred."""
+    out = (C.c_int64 * 2)()
+    if lib().ionode_dense_defer_plan(C.byref(desc), int(bool(want_current)), C.byref(out)) != 0:
+        raise IonodeError(last_error())
+    return {"capacity": int(out[0]), "workspace_bytes": int(out[1])}
 
 
 def kernel_name(desc):
@@ -353,7 +367,14 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
             _dev_ptr(vtab, torch.float64, "v_at_outputs", (P, Nt))
         if vtab is not None:
             desc.v_at_outputs = vtab.data_ptr()
-    rc = lib().ionode_dopri5(
+    # deferred dense output: the record workspace comes from torch's caching allocator (repeat calls cost nothing) and goes back to it
+    # when this call returns -- in stream order, which holds for torch's current stream only, so a foreign stream defers nothing
+    ws = None
+    if stream is None and prot_t is None and y is not None:
+        plan = dense_defer_plan(desc, i_out is not None)
+        if plan["capacity"] > 0:
+            ws = torch.empty((plan["workspace_bytes"],), dtype=torch.uint8, device=dev)
+    rc = lib().ionode_dopri5_deferred(
         C.byref(desc),
         _dev_ptr(mlp_packed, torch.float32, "mlp_packed"),
         _dev_ptr(params, torch.float64, "params", (B, params.shape[1])),
@@ -367,6 +388,8 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
         _dev_ptr(status, torch.int32, "status", (B,)),
         _dev_ptr(st, torch.int64, "stats", (B, 4)) if st is not None else None,
         C.c_void_p(s),
+        C.c_void_p(ws.data_ptr()) if ws is not None else None,
+        ws.numel() if ws is not None else 0,
     )
     if rc != 0:
         raise IonodeError(f"ionode_dopri5 failed ({rc}): {last_error()}")

@@ -226,6 +226,40 @@
       const bool exact = a.te_exact != 0;
       const bool want_i = (a.i_out != nullptr) || (a.sse_out != nullptr);
       const bool ugrid = a.prot_t == nullptr;
+      // ---- deferred dense output (KernelForm::defer, a record workspace given): the step leaves ONE record to ionode_dense_expand_kernel
+      // instead of evaluating its samples here.  Lanes 16 q + j of all four wavefronts hold slot j's values: replica 4 wis + q stores
+      // 16-byte chunk 4 wis + q of the row -- one store instruction per wavefront.  A trajectory whose records are full emits inline.
+      int n_emit = n_out;
+      if constexpr (F::defer) {
+        if (a.defer_rec != nullptr) {
+          using Rec = DenseRecord<D>;
+          const bool rec_now = n_out > 0 && nrec < a.defer_cap;
+          const int rq = lane >> 4;
+          auto chunk = [&](int r) {   // (r: a constant once unrolled)
+            if (r == 0) return make_double2(t0, den);
+            if (r == 1) return make_double2(rden, Rec::pack_cursor(oi_before, n_out));
+            const int e = 2 * (r - 2);   // coefficient pair e, e + 1 of [c][d]
+            return make_double2((double)ic[e / D][e % D], (double)ic[(e + 1) / D][(e + 1) % D]);
+          };
+          double2 *__restrict__ row = reinterpret_cast<double2 *>(a.defer_rec + ((size_t)traj * (size_t)a.defer_cap + (size_t)nrec) * Rec::ROW);
+#pragma unroll
+          for (int w = 0; 4 * w < Rec::CHUNKS; ++w) {
+            if (wis == w) {
+              double2 v = chunk(4 * w);
+#pragma unroll
+              for (int qq = 1; qq < 4; ++qq) {
+                if (4 * w + qq < Rec::CHUNKS) {
+                  const double2 c = chunk(4 * w + qq);
+                  if (rq == qq) v = c;
+                }
+              }
+              if (rec_now && 4 * w + rq < Rec::CHUNKS) row[4 * w + rq] = v;
+            }
+          }
+          if (rec_now) { n_emit = 0; ++nrec; }
+        }
+      }
+      if (!F::defer || __ballot(n_emit > 0) != 0ull) {
       int o_[NS], n_[NS], ip_[NS];
       double tk_[NS], plo_[NS], phi_[NS];
       bool inr_[NS];
@@ -234,7 +268,7 @@
       for (int k = 0; k < NS; ++k) {
         const int jj = wis + WPS * k;
         o_[k] = __builtin_amdgcn_readlane(oi, jj);
-        n_[k] = (LPS >= WPS || jj < LPS) ? __builtin_amdgcn_readlane(n_out, jj) : 0;
+        n_[k] = (LPS >= WPS || jj < LPS) ? __builtin_amdgcn_readlane(n_emit, jj) : 0;
         pv_[k] = a.prot_v + (size_t)__builtin_amdgcn_readlane(pidx, jj) * a.Np;
         tk_[k] = 0.0;
         if (lane < n_[k]) tk_[k] = exact ? te_at(o_[k] + lane) : a.t_eval[o_[k] + lane];
@@ -300,6 +334,7 @@
           }
         }
       }
+      }   // (deferring tile: no trajectory of the tile emits inline this attempt)
       oi += n_out;
       } else {
       // ---- lane-wise kernels on a verified uniform output grid: WORK-LIST emission.

@@ -203,6 +203,34 @@ int plan_mlp(const ionode_desc *d, Plan *pl, const Ask &k) {
   return IONODE_OK;
 }
 
+// Deferred dense output (ionode_dense_expand.hpp): the record capacity per trajectory and the workspace bytes of a plan, both 0 when
+// nothing is deferred -- a variant without KernelForm::defer, the fused objective, IONODE_DEFER_DENSE=0.  The records may take a
+// quarter of the bytes of the requested outputs; fewer than 64 records per trajectory are not worth the second kernel.
+// IONODE_DEFER_DENSE_CAP=n forces a capacity (dev overrides for A/B runs and tests, read per plan like IONODE_TILE_SHRINK).
+struct DeferPlan {
+  int64_t cap = 0, bytes = 0;
+};
+DeferPlan plan_defer(const ionode_desc *d, const Plan &pl, bool want_i) {
+  DeferPlan p;
+  if (!pl.v->defer || d->sse_out != nullptr || d->n_state != 2) return p;
+  const char *sw = getenv("IONODE_DEFER_DENSE");
+  if (sw != nullptr && sw[0] != '\0' && atoi(sw) == 0) return p;
+  using Rec = ionode::DenseRecord<2>;
+  const int64_t B = d->n_traj, Nt = d->n_out;
+  const char *fc = getenv("IONODE_DEFER_DENSE_CAP");
+  int64_t cap = (fc != nullptr && fc[0] != '\0') ? atoll(fc) : 0;
+  const bool forced = cap > 0;
+  if (!forced) {
+    const int64_t out_bytes = B * Nt * 2 * (d->state_f32 ? 4 : 8) + (want_i ? B * Nt * 8 : 0);
+    cap = (out_bytes / 4) / (B * Rec::BYTES);
+  }
+  cap = std::min<int64_t>(cap, Nt - 1);
+  if (cap < (forced ? 1 : 64)) return p;
+  p.cap = cap;
+  p.bytes = (int64_t)Rec::workspace_bytes(B, cap);
+  return p;
+}
+
 int make_plan(const ionode_desc *d, Plan *pl, bool want_current = false, bool explicit_grid = false) {
   if (!d) { set_err("null descriptor"); return IONODE_ERR_ARG; }
 #ifdef IONODE_STAMPS
@@ -507,9 +535,24 @@ const char *ionode_last_kernel_name(void) { return g_last_kernel; }
 
 int32_t ionode_lane_wise_from(int32_t model, int32_t mlp_width) { return lane_wise_from(model, mlp_width); }
 
-int ionode_dopri5(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
-                  const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
-                  void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream) {
+int ionode_dense_defer_plan(const ionode_desc *d, int32_t want_current, int64_t out[2]) {
+  Plan pl;
+  const int rc = make_plan(d, &pl, want_current != 0 || (d && d->sse_out != nullptr));
+  if (rc != IONODE_OK) return rc;
+  const DeferPlan dp = plan_defer(d, pl, want_current != 0);
+  out[0] = dp.cap;
+  out[1] = dp.bytes;
+  return IONODE_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// ionode_dopri5 and ionode_dopri5_deferred: the solve and, when the plan defers the dense output into `workspace`, its expansion
+int dopri5_impl(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
+                const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
+                void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace, int64_t workspace_bytes) {
   Plan pl;
   const int rc = make_plan(d, &pl, i_out != nullptr || d->sse_out != nullptr, prot_t != nullptr);
   if (rc != IONODE_OK) return rc;
@@ -549,10 +592,48 @@ int ionode_dopri5(const ionode_desc *d, const float *mlp_packed, const double *p
   a.te_rdt = a.te_dt > 0.0 ? 1.0 / a.te_dt : 0.0;
   a.te_exact = (a.te_dt > 0.0 && d->t_eval_exact) ? 1 : 0;
   a.tile_shrink = pl.tile_shrink ? 1 : 0;
-  const hipError_t e = pl.v->fn(a, pl.grid, pl.lds, reinterpret_cast<hipStream_t>(stream));
+  // deferred dense output: the plan's capacity again (with what this call really asks for); a workspace it does not use is ignored
+  DeferPlan dp;
+  if (workspace != nullptr && prot_t == nullptr && y_out != nullptr) dp = plan_defer(d, pl, i_out != nullptr);
+  if (dp.cap > 0) {
+    if (workspace_bytes < dp.bytes || (reinterpret_cast<uintptr_t>(workspace) & 15) != 0) {
+      set_err("ionode_dopri5_deferred: workspace smaller than ionode_dense_defer_plan() asks for, or not 16-byte aligned");
+      return IONODE_ERR_ARG;
+    }
+    a.defer_count = static_cast<int32_t *>(workspace);
+    a.defer_rec = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + ionode::DenseRecord<2>::records_offset(d->n_traj));
+    a.defer_cap = (int32_t)dp.cap;
+  }
+  hipError_t e = pl.v->fn(a, pl.grid, pl.lds, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) { set_err("kernel launch failed: %s", hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
+  if (dp.cap > 0) {
+    const dim3 grid((unsigned)std::min<int64_t>((dp.cap + ionode::kExpandRecordsPerWg - 1) / ionode::kExpandRecordsPerWg, ionode::kExpandMaxBlocks),
+                    (unsigned)std::min(d->n_traj, 65535));
+    if (d->state_f32) hipLaunchKernelGGL((ionode::ionode_dense_expand_kernel<float, 2>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL((ionode::ionode_dense_expand_kernel<double, 2>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
+    e = hipGetLastError();
+    if (e != hipSuccess) { set_err("kernel launch failed: %s", hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
+  }
   g_last_kernel = pl.v->name;
   return IONODE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ionode_dopri5(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
+                  const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
+                  void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream) {
+  return dopri5_impl(d, mlp_packed, params, prot_v, prot_t, prot_of_traj, y0, t_eval, y_out, i_out, status, stats, stream, nullptr, 0);
+}
+
+int ionode_dopri5_deferred(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
+                           const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
+                           void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace,
+                           int64_t workspace_bytes) {
+  return dopri5_impl(d, mlp_packed, params, prot_v, prot_t, prot_of_traj, y0, t_eval, y_out, i_out, status, stats, stream, workspace,
+                     workspace_bytes);
 }
 
 int ionode_protocol_at_outputs(const ionode_desc *d, const double *prot_v, const double *prot_t, const double *t_eval,

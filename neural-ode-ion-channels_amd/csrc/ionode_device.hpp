@@ -34,6 +34,7 @@
 #include "ionode_form.hpp"
 #include "ionode_kargs.hpp"   // KArgs, protocol_index / protocol_from / protocol_v
 #include "ionode_math.hpp"
+#include "ionode_dense_expand.hpp"   // DenseRecord: what a deferring tile writes per accepted step
 
 namespace ionode {
 
@@ -58,6 +59,7 @@ struct LwLds {
   static __host__ __device__ constexpr int clist_off(int D, int tail) { return trl_off(D, tail) + 256; }
   static __host__ __device__ constexpr int bytes(int D, int tail) { return clist_off(D, tail) + 1024; }
 };
+static_assert(LwLds::rowb(2) == DenseRecord<2>::BYTES && LwLds::rowb(6) == DenseRecord<6>::BYTES, "the deferred-output record is the lane-wise kernels' row");
 static_assert(LwLds::bytes(2, 1) <= 10240 && LwLds::bytes(2, 0) <= 12800 && LwLds::bytes(2, 2) <= 12800, "2-state kernels: 16 / 12 wavefronts per compute unit");
 
 }  // namespace ionode
@@ -286,6 +288,7 @@ __global__ void __launch_bounds__((KernelForm<MODEL, G, RT, NT, PD, TAIL>::block
   int oi = 1;  // next output index
   int nacc = 0, nrej = 0;
   int since = 0;  // attempts since the last emitted output (torchdiffeq counts max_num_steps per _advance call)
+  [[maybe_unused]] int nrec = 0;  // (KernelForm::defer) dense-output records this trajectory has written
   int status = IONODE_STATUS_OK;
   bool active = valid && Nt > 1;
   const S nan_s = (S)__builtin_nan("");
@@ -396,6 +399,9 @@ __global__ void __launch_bounds__((KernelForm<MODEL, G, RT, NT, PD, TAIL>::block
   }
   if (a.sse_out != nullptr && valid && lane < LPS && (WPS == 1 || (lane % WPS) == wis))
     a.sse_out[traj] = (status == IONODE_STATUS_OK) ? sse : __builtin_inf();  // the reference's time-limit rule: inf (train-d0.py:430-431)
+  if constexpr (F::defer) {
+    if (a.defer_rec != nullptr && valid && primary) a.defer_count[traj] = nrec;
+  }
   if (valid && primary) {
     a.status[traj] = status;
     if (a.stats) {

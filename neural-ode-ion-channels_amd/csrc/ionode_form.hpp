@@ -79,6 +79,9 @@ template <int MODEL, int G, int RT, int NT, int PD, int TAIL> struct KernelForm 
   static constexpr int waves_per_simd = t64 ? IONODE_T64_WAVES : (MODEL == IONODE_MODEL_HH2 ? 2 : 1);
   // the lean N = 200 16-tile finishes on the 4-trajectory net once <= 4 of its trajectories are live (MlpShrink4)
   static constexpr bool shrink = net == Net::Tile && G == 4 && NT == 13 && PD == 13 && TAIL == 8;
+  // ... and, given a record workspace, leaves the dense output of its accepted steps to ionode_dense_expand_kernel: a step writes one
+  // record (ionode_dense_expand.hpp DenseRecord) instead of evaluating and storing its samples between two evaluations of the net
+  static constexpr bool defer = shrink;
 
   using Tile = MlpTile<G, (t64 ? 1 : (RT > 0 ? RT : 1)), (NT > 0 ? NT : 1), ((PD > 0 && net != Net::Lane) ? PD : 1), nsets>;
   using Mlp = std::conditional_t<net == Net::None, NoMlp,

@@ -48,6 +48,10 @@ struct KArgs {
   const int32_t *order; // optional launch order (a permutation of 0..B-1): launch slot s integrates trajectory order[s]; every
                         // input and output stays at the trajectory's own index -- only the tiling / lane assignment changes
   int32_t tile_shrink;  // lean N = 200 16-tile: 1 = switch to the 4-trajectory net once <= 4 of the tile's trajectories are live (MlpShrink4)
+  // deferred dense output (KernelForm::defer; NULL / 0: every step emits its samples itself), indexed by TRAJECTORY, not by launch slot:
+  int32_t *defer_count; // [B] records a trajectory wrote (written with its final scalars) ...
+  double *defer_rec;    // ... of [B][defer_cap][DenseRecord<D>::ROW] fp64 (ionode_dense_expand.hpp); a trajectory whose records are
+  int32_t defer_cap;    // full emits its later steps inline
 };
 
 // Uniform protocol grid, in two halves so that a caller can issue the two sample loads of several lookups back to back:

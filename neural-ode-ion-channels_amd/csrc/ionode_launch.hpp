@@ -16,6 +16,7 @@ struct Variant {
   int traj_per_tile;   // trajectories of one tile (a workgroup; lane-wise kernels: a wavefront)
   int lds_key;         // lane-wise kernels: the variant key of their LDS layout (LwLds)
   bool lane_wise, shrink;
+  bool defer;          // leaves its dense output to ionode_dense_expand_kernel when given a record workspace (KernelForm::defer)
   size_t (*lds_bytes)(int L, int NT);   // LDS bytes of the variant's net for L hidden layers (NT: the run-time-width tile's k-tiles)
   LaunchFn fn;
   const char *name;  // as rocprofv3 --kernel-trace prints it
@@ -51,7 +52,7 @@ hipError_t launch(const KArgs &a, unsigned grid, size_t lds, hipStream_t s) {
 template <int MODEL, typename S, int F32, int G, int RT, int NT, int PD, int TAIL>
 constexpr Variant make_variant(const char *name) {
   using F = KernelForm<MODEL, G, RT, NT, PD, TAIL>;
-  return Variant{MODEL, F32, G, NT, F::net, F::lean, F::traj_per_tile, F::lds_key, F::lane_wise, F::shrink, &net_lds_bytes<F>,
+  return Variant{MODEL, F32, G, NT, F::net, F::lean, F::traj_per_tile, F::lds_key, F::lane_wise, F::shrink, F::defer, &net_lds_bytes<F>,
                  &launch<MODEL, S, G, RT, NT, PD, TAIL>, name};
 }
 
