@@ -178,8 +178,18 @@ int ionode_dopri5(const ionode_desc *d, const float *mlp_packed, const double *p
  * ionode_dopri5_deferred(): ionode_dopri5() plus `workspace` (DEVICE, 16-byte aligned, at least the plan's bytes, contents
  * undefined before and after) and its size.  workspace == NULL, or a descriptor whose plan defers nothing (an explicit prot_t
  * included), is exactly ionode_dopri5(); IONODE_ERR_ARG for a workspace smaller than the plan's.
+ *
+ * The solve kernel's tail (new symbol ionode_dense_tail_plan; everything above unchanged).  A launch lasts as long as its slowest tile,
+ * so the tiles that end early expand their own records before they leave, on compute units that would otherwise idle, and store
+ * -(records + 1) as the trajectory's count; the follow-up kernel expands the trajectories with a positive count.  A finish counter
+ * ranks the tiles (one atomic add per tile, nothing waits on it); it lives in the workspace's LAST record slot, which is used
+ * internally: with the tail on a trajectory fills capacity - 1 records.  ionode_dense_tail_plan(): pure host code.  out = {tiles that
+ * expand in the solve kernel (the first out[0] to end), records a trajectory may fill}; {0, capacity} where the tail is off (capacity
+ * < 2, IONODE_DEFER_TAIL=0).  The default is 5/8 of the tiles, rounded down; IONODE_DEFER_TAIL=all: every tile,
+ * IONODE_DEFER_TAIL_RANK=n: n tiles (development switches, read per plan).
  */
 int ionode_dense_defer_plan(const ionode_desc *d, int32_t want_current, int64_t out[2]);
+int ionode_dense_tail_plan(const ionode_desc *d, int32_t want_current, int64_t out[2]);
 int ionode_dopri5_deferred(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
                            const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
                            void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace,

@@ -31,7 +31,7 @@ EXPORTS = (
     "ionode_dopri5_backward_sse_gc", "ionode_dopri5_backward_recompute_sse", "ionode_dopri5_backward_sweep_sse",
     "ionode_grad_partial_floats", "ionode_grad_reduce", "ionode_grad_reduce_unit", "ionode_grad_reduce_slabs", "ionode_grad_last_error",
     "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh", "ionode_regress_plan",
-    "ionode_dense_defer_plan", "ionode_dopri5_deferred",
+    "ionode_dense_defer_plan", "ionode_dense_tail_plan", "ionode_dopri5_deferred",
 )
 
 # the backward sweep's entry points: their buffers in ABI order -- between (d, it_begin, it_end, n_iter) and stream (include/ionode.h;
@@ -121,6 +121,8 @@ def lib():
         L.ionode_dopri5_deferred.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 13 + [C.c_int64]
         L.ionode_dense_defer_plan.restype = C.c_int
         L.ionode_dense_defer_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int64 * 2)]
+        L.ionode_dense_tail_plan.restype = C.c_int
+        L.ionode_dense_tail_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int64 * 2)]
         L.ionode_grad_last_error.restype = C.c_char_p
         for fn in (L.ionode_grad_image_floats, L.ionode_grad_record_floats, L.ionode_grad_partial_floats):
             fn.restype = C.c_size_t
@@ -222,6 +224,15 @@ def dense_defer_plan(desc, want_current):
     return {"capacity": int(out[0]), "workspace_bytes": int(out[1])}
 
 
+def dense_tail_plan(desc, want_current):
+    """The solve kernel's tail (ionode_dense_tail_plan, pure host code): how many tiles, in the order they end, expand their own records
+    inside the solve kernel, and the records a trajectory may fill (capacity - 1 with the tail on: the last slot holds the counter)."""
+    out = (C.c_int64 * 2)()
+    if lib().ionode_dense_tail_plan(C.byref(desc), int(bool(want_current)), C.byref(out)) != 0:
+        raise IonodeError(last_error())
+    return {"tail_rank": int(out[0]), "usable_capacity": int(out[1])}
+
+
 def kernel_name(desc):
     return lib().ionode_kernel_name(C.byref(desc)).decode()
 
@@ -269,13 +280,16 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
            prot_t0=0.0, prot_dt=1.0, prot_of_traj=None, rtol=1e-7, atol=1e-9, v_oob=-80.0, max_steps=0,
            max_total_steps=0, max_step=0.0, ckpt=None, current=False, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False, tile_waves=0, stats=True,
            step_log=None, t_eval_hint="auto", t_eval_exact=None, sse_ref=None, states=True, out=None, stream=None,
-           v_at_outputs="auto", traj_per_image=0, launch_order="auto"):
+           v_at_outputs="auto", traj_per_image=0, launch_order="auto", workspace=None):
     """Launch one batched solve.  Every tensor lives on the current HIP device.
 
     launch_order: None (index order), an int32 device permutation [B] (ionode_desc.launch_order: slot s integrates trajectory
     order[s]; results stay at the trajectories' own indices, bit-identical to index order), or "auto": protocol-major order for
     the one-trajectory-per-lane kernels when several protocols are interleaved (the 64 lanes of a wavefront then interpolate
     one protocol instead of 64: -5 % on 393 216 HH trajectories over 64 protocols).
+
+    workspace: optional uint8 device tensor for the deferred dense output (at least dense_defer_plan's bytes, 16-byte aligned) instead
+    of one from torch's allocator -- a caller that wants to read the record counts back (tests) keeps it.
 
     params [B, n_params] f64, prot_v [P, Np] f64, y0 [B, D] f32|f64 (selects the state dtype),
     t_eval [Nt] f64.  Returns dict(y [B, Nt, D], i [B, Nt] | None, status [B] i32, stats [B, 4] i64 | None);
@@ -373,7 +387,11 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
     if stream is None and prot_t is None and y is not None:
         plan = dense_defer_plan(desc, i_out is not None)
         if plan["capacity"] > 0:
-            ws = torch.empty((plan["workspace_bytes"],), dtype=torch.uint8, device=dev)
+            if workspace is not None:
+                _dev_ptr(workspace, torch.uint8, "workspace")
+                if workspace.numel() < plan["workspace_bytes"]:
+                    raise IonodeError(f"workspace: {workspace.numel()} bytes, the plan asks for {plan['workspace_bytes']}")
+            ws = workspace if workspace is not None else torch.empty((plan["workspace_bytes"],), dtype=torch.uint8, device=dev)
     rc = lib().ionode_dopri5_deferred(
         C.byref(desc),
         _dev_ptr(mlp_packed, torch.float32, "mlp_packed"),

@@ -233,7 +233,7 @@
       if constexpr (F::defer) {
         if (a.defer_rec != nullptr) {
           using Rec = DenseRecord<D>;
-          const bool rec_now = n_out > 0 && nrec < a.defer_cap;
+          const bool rec_now = n_out > 0 && nrec < a.defer_fill;
           const int rq = lane >> 4;
           auto chunk = [&](int r) {   // (r: a constant once unrolled)
             if (r == 0) return make_double2(t0, den);

@@ -231,6 +231,33 @@ DeferPlan plan_defer(const ionode_desc *d, const Plan &pl, bool want_i) {
   return p;
 }
 
+// The solve kernel's tail (ionode_device.hpp): how many tiles, in the order they end, expand their own records before they leave, and
+// the records a trajectory may fill.  The launch lasts as long as its slowest tile; the first kDeferTailEighths / 8 of the tiles end at
+// least twice a tile's expansion time before it does (profiles/defer_tail.md), the rest leave their records to the follow-up kernel.
+// The finish counter lives in the workspace's last record slot, so with the tail on a trajectory fills cap - 1 records (the stride and
+// the workspace stay what ionode_dense_defer_plan reports).  IONODE_DEFER_TAIL=0: no tile, IONODE_DEFER_TAIL=all: every tile,
+// IONODE_DEFER_TAIL_RANK=n: n tiles (dev overrides for A/B runs and tests, read per plan like IONODE_TILE_SHRINK).
+constexpr int64_t kDeferTailEighths = 5;
+struct TailPlan {
+  int64_t rank = 0, fill = 0;
+};
+TailPlan plan_tail(const Plan &pl, const DeferPlan &dp) {
+  TailPlan t;
+  t.fill = dp.cap;
+  if (dp.cap < 2) return t;
+  const int64_t tiles = (int64_t)pl.grid;
+  t.rank = tiles * kDeferTailEighths / 8;
+  const char *fr = getenv("IONODE_DEFER_TAIL_RANK");
+  if (fr != nullptr && fr[0] != '\0') t.rank = std::max<int64_t>(0, std::min<int64_t>(atoll(fr), tiles));
+  const char *sw = getenv("IONODE_DEFER_TAIL");
+  if (sw != nullptr && sw[0] != '\0') {
+    if (strcmp(sw, "all") == 0) t.rank = tiles;
+    else if (atoi(sw) == 0) t.rank = 0;
+  }
+  if (t.rank > 0) t.fill = dp.cap - 1;
+  return t;
+}
+
 int make_plan(const ionode_desc *d, Plan *pl, bool want_current = false, bool explicit_grid = false) {
   if (!d) { set_err("null descriptor"); return IONODE_ERR_ARG; }
 #ifdef IONODE_STAMPS
@@ -545,6 +572,16 @@ int ionode_dense_defer_plan(const ionode_desc *d, int32_t want_current, int64_t 
   return IONODE_OK;
 }
 
+int ionode_dense_tail_plan(const ionode_desc *d, int32_t want_current, int64_t out[2]) {
+  Plan pl;
+  const int rc = make_plan(d, &pl, want_current != 0 || (d && d->sse_out != nullptr));
+  if (rc != IONODE_OK) return rc;
+  const TailPlan tp = plan_tail(pl, plan_defer(d, pl, want_current != 0));
+  out[0] = tp.rank;
+  out[1] = tp.fill;
+  return IONODE_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -603,12 +640,21 @@ int dopri5_impl(const ionode_desc *d, const float *mlp_packed, const double *par
     a.defer_count = static_cast<int32_t *>(workspace);
     a.defer_rec = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + ionode::DenseRecord<2>::records_offset(d->n_traj));
     a.defer_cap = (int32_t)dp.cap;
+    const TailPlan tp = plan_tail(pl, dp);
+    a.defer_fill = (int32_t)tp.fill;
+    a.defer_tail_rank = (int32_t)tp.rank;
+    if (tp.rank > 0) {
+      // the tail block: the last record slot (no trajectory fills it), zeroed in stream order ahead of the solve
+      a.defer_tail = reinterpret_cast<int32_t *>(a.defer_rec + ((size_t)d->n_traj * (size_t)dp.cap - 1) * ionode::DenseRecord<2>::ROW);
+      const hipError_t em = hipMemsetAsync(a.defer_tail, 0, ionode::DenseRecord<2>::BYTES, reinterpret_cast<hipStream_t>(stream));
+      if (em != hipSuccess) { set_err("hipMemsetAsync failed: %s", hipGetErrorString(em)); return IONODE_ERR_LAUNCH; }
+    }
   }
   hipError_t e = pl.v->fn(a, pl.grid, pl.lds, reinterpret_cast<hipStream_t>(stream));
   if (e != hipSuccess) { set_err("kernel launch failed: %s", hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
   if (dp.cap > 0) {
-    const dim3 grid((unsigned)std::min<int64_t>((dp.cap + ionode::kExpandRecordsPerWg - 1) / ionode::kExpandRecordsPerWg, ionode::kExpandMaxBlocks),
-                    (unsigned)std::min(d->n_traj, 65535));
+    const int64_t blocks = std::min<int64_t>((dp.cap + ionode::kExpandRecordsPerWg - 1) / ionode::kExpandRecordsPerWg, ionode::kExpandMaxBlocks);
+    const dim3 grid((unsigned)std::min<int64_t>((int64_t)d->n_traj * blocks, ionode::kExpandGrid));
     if (d->state_f32) hipLaunchKernelGGL((ionode::ionode_dense_expand_kernel<float, 2>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     else hipLaunchKernelGGL((ionode::ionode_dense_expand_kernel<double, 2>), grid, dim3(256), 0, reinterpret_cast<hipStream_t>(stream), a);
     e = hipGetLastError();

@@ -166,6 +166,7 @@ __global__ void __launch_bounds__((KernelForm<MODEL, G, RT, NT, PD, TAIL>::block
   unsigned char *const lsm = smem_t + lw_off;
   STAMP_DECL
 #ifdef IONODE_STAMPS
+  [[maybe_unused]] const unsigned long long wall0_ = wall_clock64();
   if constexpr (MT::MLP) mlp.sp = &stamps_;
 #endif
 
@@ -399,9 +400,6 @@ __global__ void __launch_bounds__((KernelForm<MODEL, G, RT, NT, PD, TAIL>::block
   }
   if (a.sse_out != nullptr && valid && lane < LPS && (WPS == 1 || (lane % WPS) == wis))
     a.sse_out[traj] = (status == IONODE_STATUS_OK) ? sse : __builtin_inf();  // the reference's time-limit rule: inf (train-d0.py:430-431)
-  if constexpr (F::defer) {
-    if (a.defer_rec != nullptr && valid && primary) a.defer_count[traj] = nrec;
-  }
   if (valid && primary) {
     a.status[traj] = status;
     if (a.stats) {
@@ -410,6 +408,48 @@ __global__ void __launch_bounds__((KernelForm<MODEL, G, RT, NT, PD, TAIL>::block
       st[1] = nrej;
       st[2] = 2 + 6 * ((int64_t)nacc + nrej);
       st[3] = status;
+    }
+  }
+  // ---- deferred dense output: the tile's record counts, and the TAIL.  The launch lasts as long as its slowest tile (one tile per
+  // compute unit at the headline shape), so a tile that ends early expands its own records here, on a compute unit that would idle until
+  // the launch ends, and only the late tiles' records are left for ionode_dense_expand_kernel.  Early is decided by ONE atomic add on a
+  // finish counter: the tile reads its rank once and nothing ever waits on the counter.
+  if constexpr (F::defer) {
+    if (a.defer_rec != nullptr) {
+      int left = nrec;
+      if (a.defer_tail_rank > 0) {
+        // the asm stream leaves the next evaluation's weight loads in flight (into a[0:91]), and the workgroup's LDS is dead from here on
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __syncthreads();
+        int *const rank_lds = reinterpret_cast<int *>(smem);
+        if (threadIdx.x == 0) *rank_lds = atomicAdd(a.defer_tail, 1);
+        __syncthreads();
+        const int rank = __builtin_amdgcn_readfirstlane(*rank_lds);
+#ifdef IONODE_STAMPS
+        const unsigned long long wall1_ = wall_clock64();
+#endif
+        if (rank < a.defer_tail_rank) {
+          // records are written by lanes of all four wavefronts: every store acknowledged (above), visible device-wide, then the barrier
+          __threadfence();
+          __syncthreads();
+          __threadfence();
+#pragma unroll 1
+          for (int jj = 0; jj < LPS; ++jj) {
+            const int cj = __builtin_amdgcn_readlane(nrec, jj);   // (a slot past the batch, a NaN y0: no record)
+            if (cj > 0) dense_expand_records<S, D, kExpandAheadTail>(a, __builtin_amdgcn_readlane(traj, jj), wave, cj, G, lane);
+          }
+          left = -(nrec + 1);
+        }
+#ifdef IONODE_STAMPS
+        // per tile, 100 MHz wall clock (tools/defer_tail_stamps.py): start, end of the solve, end of the tail, behind the per-tile block
+        if (threadIdx.x == 0 && a.step_log != nullptr && 4 * a.step_log_cap >= 64 + 4 * (int64_t)gridDim.x) {
+          double *const w_ = a.step_log + 64 + gridDim.x + 3 * (size_t)blockIdx.x;
+          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (the tail's stores acknowledged)
+          w_[0] = (double)wall0_; w_[1] = (double)wall1_; w_[2] = (double)wall_clock64();
+        }
+#endif
+      }
+      if (valid && primary) a.defer_count[traj] = left;
     }
   }
 }

@@ -52,6 +52,11 @@ struct KArgs {
   int32_t *defer_count; // [B] records a trajectory wrote (written with its final scalars) ...
   double *defer_rec;    // ... of [B][defer_cap][DenseRecord<D>::ROW] fp64 (ionode_dense_expand.hpp); a trajectory whose records are
   int32_t defer_cap;    // full emits its later steps inline
+  int32_t defer_fill;   // records a trajectory may fill, <= defer_cap (the records' stride stays defer_cap)
+  // the solve kernel's tail (ionode_device.hpp): a tile that ends with a finish rank below defer_tail_rank expands its own records on
+  // its otherwise idle compute unit and leaves -(records + 1) in defer_count; 0: every tile leaves its records to the follow-up kernel
+  int32_t defer_tail_rank;
+  int32_t *defer_tail;  // the tail block (the workspace's last record slot, which defer_fill keeps free): [0] tiles that have ended
 };
 
 // Uniform protocol grid, in two halves so that a caller can issue the two sample loads of several lookups back to back:
