@@ -147,24 +147,15 @@
     // then div_by() per sample -- the same correctly rounded quotient
     const double den = t1 - t0;
     const double rden = 1.0 / den;
-    constexpr int ROW = 4 + 5 * D;  // doubles per LDS row, 16-byte aligned rows
+    using IRow = InterpRow<D>;      // an LDS row of the lane-wise kernels (16-byte aligned)
     S ic[LW ? 1 : 5][LW ? 1 : D];   // e, d, c, b, a -- tile kernels keep them in registers (broadcast by v_readlane)
     {
+      // (the weights and the per-component call are written in this shape on purpose: through a routine for the weights, or without
+      // the lambda, hipcc schedules the 6-state kernels differently -- fused objective forward +3.7 %, profiles/interp_refactor.md)
       S bm[7];
 #pragma unroll
       for (int jx = 0; jx < 7; ++jx) bm[jx] = dts * (S)kCmid[jx];
-      auto fit = [&](int d, S *c5) {
-        S s = k[0][d] * bm[0];
-#pragma unroll
-        for (int jx = 1; jx < 7; ++jx) s = s + k[jx][d] * bm[jx];
-        const S YM = y[d] + s;
-        const S F0 = k[0][d], F1 = k[6][d], Y0 = y[d], Y1 = yi[d];
-        c5[4] = ((S)2 * dts) * (F1 - F0) - (S)8 * (Y1 + Y0) + (S)16 * YM;
-        c5[3] = dts * ((S)5 * F0 - (S)3 * F1) + (S)18 * Y0 + (S)14 * Y1 - (S)32 * YM;
-        c5[2] = dts * (F1 - (S)4 * F0) - (S)11 * Y0 - (S)5 * Y1 + (S)16 * YM;
-        c5[1] = dts * F0;
-        c5[0] = Y0;
-      };
+      auto fit = [&](int d, S *c5) { interp_fit<S, D>(dts, bm, y, yi, k, d, c5); };
       if constexpr (LW) {
         // Lane-wise kernels: a lane's interpolant (t0, step length, its reciprocal, 5 x D coefficients) goes to its LDS row;
         // the wavefront then reads the emitting trajectory's row at a uniform address (7 broadcast ds_read_b128 for D = 2)
@@ -174,14 +165,13 @@
         double2 *row = reinterpret_cast<double2 *>(lsm + lane * ROWB);
         row[0] = make_double2(t0, den);
         row[1] = make_double2(rden, 0.0);
-        static_assert(D % 2 == 0, "rows hold component pairs");
 #pragma unroll
         for (int d = 0; d < D; d += 2) {
           S ca[5], cb2[5];
           fit(d, ca);
           fit(d + 1, cb2);
 #pragma unroll
-          for (int c = 0; c < 5; ++c) row[2 + (c * D + d) / 2] = make_double2((double)ca[c], (double)cb2[c]);
+          for (int c = 0; c < 5; ++c) row[IRow::coef(c, d) / 2] = make_double2((double)ca[c], (double)cb2[c]);
           if constexpr (D > 2) __builtin_amdgcn_sched_barrier(0);
         }
       } else {
@@ -194,6 +184,11 @@
         }
       }
     }
+    // the interpolant of emitting trajectory jj, wave-uniform: from its LDS row, or from its lane's registers
+    auto load_interp = [&](Interp<S, D> &itp, int jj) {
+      if constexpr (LW) itp.from_row(reinterpret_cast<const double2 *>(lsm + jj * ROWB));
+      else itp.from_lanes(t0, den, rden, ic, jj);
+    };
     STAMP(stamps_, 8);  // slot 8: interpolant fit
     if (LEAN || LEANM || a.te_dt > 0.0) {
       // ---- output cursor, lane-parallel: how many requested times fall in (t0, t1] for MY trajectory? ----
@@ -286,12 +281,8 @@
         const int jj = wis + WPS * k;
         const int n = n_[k], o = o_[k];
         if (n > 0) {
-          const double t0b = bcast_f64(t0, jj), denb = bcast_f64(den, jj), rdenb = bcast_f64(rden, jj);
-          S cb[5][D];
-#pragma unroll
-          for (int c = 0; c < 5; ++c)
-#pragma unroll
-            for (int d = 0; d < D; ++d) cb[c][d] = bcast<S>(ic[c][d], jj);
+          Interp<S, D> itp;
+          load_interp(itp, jj);
           const int tr = __builtin_amdgcn_readlane(traj, jj);
           S *__restrict__ yo = a.y_out ? reinterpret_cast<S *>(a.y_out) + (size_t)tr * Nt * D : nullptr;
           double *__restrict__ io = a.i_out ? a.i_out + (size_t)tr * Nt : nullptr;
@@ -302,26 +293,14 @@
             double tk = tk_[k];
             if (c0 > 0 && c0 + lane < n) tk = exact ? te_at(idx) : a.t_eval[idx];
             if (c0 + lane < n) {
-              const S x = (S)div_pos(tk - t0b, denb, rdenb);  // _interp_evaluate: x = (t - t0) / (t1 - t0) in fp64, cast; running powers
               S out[D];
-              S xp = x;
-#pragma unroll
-              for (int d = 0; d < D; ++d) out[d] = cb[0][d] + x * cb[1][d];
-#pragma unroll
-              for (int c = 2; c < 5; ++c) {
-                xp = xp * x;
-#pragma unroll
-                for (int d = 0; d < D; ++d) out[d] = out[d] + xp * cb[c][d];
-              }
+              interp_eval<S, D>(itp.cb, itp.x(tk), out);
               if (yo) store_state<S, D>(yo + (size_t)idx * D, out);
               if (want_i) {
                 double vk;
                 if (c0 == 0 && ugrid) vk = inr_[k] ? protocol_from(a, plo_[k], phi_[k], ip_[k], tk) : a.v_oob;
                 else protocol_v(a, pv_[k], tk, vk);
-                S gate;
-                if (a.obs_open) gate = out[D - 1]; else gate = out[0] * out[1];
-                if (a.obs_g != 1.0) gate = (S)a.obs_g * gate;
-                const double ik = (double)gate * (vk - a.obs_e);
+                const double ik = obs_current<S, D>(a, out, vk);
                 if (io) io[idx] = ik;
                 if (refb) { const double rr = ik - refb[idx]; sacc += rr * rr; }
               }
@@ -368,7 +347,7 @@
           auto emit_packed = [&](auto wi_tag) {
             constexpr bool WI = decltype(wi_tag)::value;
             const int nch = (n_out + PK - 1) / PK;   // 1 .. 8 for the listed lanes
-            if (packed_lane) *reinterpret_cast<int2 *>(lsm + lane_e * ROWB + 24) = make_int2(oi, oi + n_out);   // the row's spare slot
+            if (packed_lane) *reinterpret_cast<int2 *>(lsm + lane_e * ROWB + IRow::SPARE * 8) = make_int2(oi, oi + n_out);   // the row's spare slot
             const int x = nch - 1;
             const unsigned long long m0 = __ballot(packed_lane && (x & 1)), m1 = __ballot(packed_lane && (x & 2)), m2 = __ballot(packed_lane && (x & 4));
             const int q = mbcnt(m0, mbcnt(emd)) + 2 * mbcnt(m1) + 4 * mbcnt(m2);
@@ -385,7 +364,7 @@
               const unsigned e = clist[t.has ? c0 + slot : (c0 < C ? c0 : 0)];
               t.jj = (int)(e & 63u);
               t.part = (int)(e >> 9);   // chunk number: the objective's partial-sum slot
-              const int2 on2 = *reinterpret_cast<const int2 *>(lsm + t.jj * ROWB + 24);
+              const int2 on2 = *reinterpret_cast<const int2 *>(lsm + t.jj * ROWB + IRow::SPARE * 8);
               t.idx0 = on2.x + (int)(e >> 6) + kk;
               t.end = on2.y;
 #pragma unroll
@@ -413,34 +392,18 @@
               const Ent cur = PREF ? nx : decode(c0);
               if constexpr (PREF) { if (c0 + 64 / PKL < C) nx = decode(c0 + 64 / PKL); }
               const int jj = cur.jj;
-              const double2 *rj = reinterpret_cast<const double2 *>(lsm + jj * ROWB);
-              const double2 h0 = rj[0];
-              const double t0b = h0.x, denb = h0.y, rdenb = rj[1].x;
-              S cb[5][D];
-#pragma unroll
-              for (int c = 0; c < 5; ++c)
-#pragma unroll
-                for (int d = 0; d < D; d += 2) {
-                  const double2 cc = rj[2 + (c * D + d) / 2];
-                  cb[c][d] = (S)cc.x; cb[c][d + 1] = (S)cc.y;
-                }
+              Interp<S, D> itp;
+              load_interp(itp, jj);
               const int tr = trl[jj];
               double tk[NSL];
               SV xv;
 #pragma unroll
               for (int u = 0; u < NSL; ++u) {
                 tk[u] = te_at(cur.idx0 + u * PKL);
-                xv[u] = (S)div_pos(tk[u] - t0b, denb, rdenb);  // _interp_evaluate: x in fp64, cast; running powers
+                xv[u] = itp.x(tk[u]);
               }
-              SV ov[D], xp = xv;
-#pragma unroll
-              for (int d = 0; d < D; ++d) ov[d] = cb[0][d] + xv * cb[1][d];
-#pragma unroll
-              for (int c = 2; c < 5; ++c) {
-                xp = xp * xv;
-#pragma unroll
-                for (int d = 0; d < D; ++d) ov[d] = ov[d] + xp * cb[c][d];
-              }
+              SV ov[D];
+              interp_eval<S, D>(itp.cb, xv, ov);
               double rr2[NSL];
 #pragma unroll
               for (int u = 0; u < NSL; ++u) {
@@ -455,10 +418,7 @@
                     double vk;
                     if constexpr (VTAB) vk = cur.vk[u];  // == protocol_v(a, pvb, t_eval[idx]), evaluated once per protocol by the pre-pass
                     else protocol_v(a, a.prot_v + (size_t)owp[jj] * a.Np, tk[u], vk);
-                    S gate;
-                    if (a.obs_open) gate = out[D - 1]; else gate = out[0] * out[1];
-                    if (a.obs_g != 1.0) gate = (S)a.obs_g * gate;
-                    const double ik = (double)gate * (vk - a.obs_e);
+                    const double ik = obs_current<S, D>(a, out, vk);
                     if (a.i_out) a.i_out[(size_t)tr * Nt + idx] = ik;
                     if (a.sse_out) { const double rr = ik - (VTAB ? cur.rf[u] : a.sse_ref[(size_t)owp[jj] * Nt + idx]); rr2[u] = rr * rr; }
                   }
@@ -519,26 +479,8 @@
         if (em && on + lane < Nt) tk_nxt = arith_t ? te_at(on + lane) : a.t_eval[on + lane];  // next trajectory's first chunk, in flight meanwhile
         if (em) prefetch_obs(jn, on);
         const int n = __builtin_amdgcn_readlane(n_out, jj);
-        double t0b, denb, rdenb;
-        S cb[5][D];
-        if constexpr (LW) {
-          const double2 *rj = reinterpret_cast<const double2 *>(lsm) + jj * (ROW / 2);
-          const double2 h0 = rj[0], h1 = rj[1];
-          t0b = h0.x; denb = h0.y; rdenb = h1.x;
-#pragma unroll
-          for (int c = 0; c < 5; ++c)
-#pragma unroll
-            for (int d = 0; d < D; d += 2) {
-              const double2 cc = rj[2 + (c * D + d) / 2];
-              cb[c][d] = (S)cc.x; cb[c][d + 1] = (S)cc.y;
-            }
-        } else {
-          t0b = bcast_f64(t0, jj); denb = bcast_f64(den, jj); rdenb = bcast_f64(rden, jj);
-#pragma unroll
-          for (int c = 0; c < 5; ++c)
-#pragma unroll
-            for (int d = 0; d < D; ++d) cb[c][d] = bcast<S>(ic[c][d], jj);
-        }
+        Interp<S, D> itp;
+        load_interp(itp, jj);
         const int tr = __builtin_amdgcn_readlane(traj, jj);
         S *__restrict__ yo = a.y_out ? reinterpret_cast<S *>(a.y_out) + (size_t)tr * Nt * D : nullptr;
         double *__restrict__ io = nullptr;
@@ -557,26 +499,14 @@
           const int idx = o + c0 + lane;
           if (c0 > 0 && c0 + lane < n) tk = arith_t ? te_at(idx) : a.t_eval[idx];
           if (c0 + lane < n) {
-            const S x = (S)div_pos(tk - t0b, denb, rdenb);  // _interp_evaluate: x = (t - t0) / (t1 - t0) in fp64, cast; running powers
             S out[D];
-            S xp = x;
-#pragma unroll
-            for (int d = 0; d < D; ++d) out[d] = cb[0][d] + x * cb[1][d];
-#pragma unroll
-            for (int c = 2; c < 5; ++c) {
-              xp = xp * x;
-#pragma unroll
-              for (int d = 0; d < D; ++d) out[d] = out[d] + xp * cb[c][d];
-            }
+            interp_eval<S, D>(itp.cb, itp.x(tk), out);
             if (yo) store_state<S, D>(yo + (size_t)idx * D, out);
             if (pvb) {
               double vk;
               if constexpr (VTAB) vk = (c0 == 0) ? vk_first : vtb[idx];  // == protocol_v(a, pvb, t_eval[idx]), evaluated once per protocol by the pre-pass
               else protocol_v(a, pvb, tk, vk);
-              S gate;
-              if (a.obs_open) gate = out[D - 1]; else gate = out[0] * out[1];
-              if (a.obs_g != 1.0) gate = (S)a.obs_g * gate;
-              const double ik = (double)gate * (vk - a.obs_e);
+              const double ik = obs_current<S, D>(a, out, vk);
               if (io) io[idx] = ik;
               if (refb) { const double rr = ik - ((VTAB && c0 == 0) ? rf_first : refb[idx]); sacc += rr * rr; }
             }
@@ -611,6 +541,8 @@
         int o = __builtin_amdgcn_readlane(oi, jj);
         const double t1b = bcast_f64(t1, jj);
         // every wavefront advances the output cursor; only the owner evaluates and stores
+        // (this site loads the interpolant in place: through load_interp the register allocation of the 4- and 32-trajectory N = 200
+        // tiles moved by 20 registers, profiles/interp_refactor.md)
         double t0b = 0.0, denb = 1.0, rdenb = 1.0;
         S cb[5][D];
         S *__restrict__ yo = nullptr;
@@ -618,14 +550,14 @@
         const double *__restrict__ pvb = nullptr;
         if (owner) {
           if constexpr (LW) {
-            const double2 *rj = reinterpret_cast<const double2 *>(lsm) + jj * (ROW / 2);
+            const double2 *rj = reinterpret_cast<const double2 *>(lsm) + jj * IRow::CHUNKS;
             const double2 h0 = rj[0], h1 = rj[1];
             t0b = h0.x; denb = h0.y; rdenb = h1.x;
 #pragma unroll
             for (int c = 0; c < 5; ++c)
 #pragma unroll
               for (int d = 0; d < D; d += 2) {
-                const double2 cc = rj[2 + (c * D + d) / 2];
+                const double2 cc = rj[IRow::coef(c, d) / 2];
                 cb[c][d] = (S)cc.x; cb[c][d + 1] = (S)cc.y;
               }
           } else {
@@ -648,26 +580,13 @@
           const double tk = (idx < Nt) ? a.t_eval[idx] : __builtin_inf();
           const bool ok = tk <= t1b;
           if (owner && ok) {
-            // _interp_evaluate: x in fp64, cast; running powers
-            const S x = (S)div_pos(tk - t0b, denb, rdenb);
             S out[D];
-            S xp = x;
-#pragma unroll
-            for (int d = 0; d < D; ++d) out[d] = cb[0][d] + x * cb[1][d];
-#pragma unroll
-            for (int c = 2; c < 5; ++c) {
-              xp = xp * x;
-#pragma unroll
-              for (int d = 0; d < D; ++d) out[d] = out[d] + xp * cb[c][d];
-            }
+            interp_eval<S, D>(cb, interp_x<S>(tk, t0b, denb, rdenb), out);
             store_state<S, D>(yo + (size_t)idx * D, out);
             if (io) {
               double vk;
               protocol_v(a, pvb, tk, vk);
-              S gate;
-              if (a.obs_open) gate = out[D - 1]; else gate = out[0] * out[1];
-              if (a.obs_g != 1.0) gate = (S)a.obs_g * gate;
-              io[idx] = (double)gate * (vk - a.obs_e);
+              io[idx] = obs_current<S, D>(a, out, vk);
             }
           }
           const int n = __builtin_popcountll(__ballot(ok));

@@ -11,21 +11,18 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ionode_interp.hpp"
 #include "ionode_kargs.hpp"
 #include "ionode_math.hpp"
 
 namespace ionode {
 
-// One accepted step's interpolant, laid out as the lane-wise kernels' LDS row (LwLds::rowb): ROW = 4 + 5 D doubles,
-//   [0] t0   [1] den = t1 - t0   [2] rden = 1 / den   [3] {int32 oi_before, int32 n_out}   [4 + c D + d] coefficient ic[c][d]
-// Coefficients are stored as doubles and cast back to the state dtype (exact for fp32).  The workspace holds an int32 count per
-// trajectory, then (16-byte aligned) the records [trajectory][cap][ROW].
-template <int D> struct DenseRecord {
-  static constexpr int ROW = 4 + 5 * D;
-  static constexpr int BYTES = ROW * 8;
-  static constexpr int CHUNKS = ROW / 2;   // 16-byte chunks: the unit a replica lane of the tile stores
-  static constexpr int T0 = 0, DEN = 1, RDEN = 2, CURSOR = 3, COEF = 4;
-  static_assert(ROW % 2 == 0, "records are whole 16-byte chunks");
+// One accepted step's interpolant: an InterpRow (ionode_interp.hpp; the lane-wise kernels' LDS row) whose spare slot holds the
+// cursor {int32 oi_before, int32 n_out}.  A 16-byte chunk is the unit a replica lane of the tile stores.  The workspace holds an
+// int32 count per trajectory, then (16-byte aligned) the records [trajectory][cap][ROW].
+template <int D> struct DenseRecord : InterpRow<D> {
+  using InterpRow<D>::BYTES;
+  static constexpr int CURSOR = InterpRow<D>::SPARE;
   static __host__ __device__ constexpr size_t records_offset(int64_t B) { return ((size_t)B * 4 + 15) & ~(size_t)15; }
   static __host__ __device__ constexpr size_t workspace_bytes(int64_t B, int64_t cap) { return records_offset(B) + (size_t)B * (size_t)cap * BYTES; }
   static __device__ __forceinline__ double pack_cursor(int oi_before, int n_out) { return __hiloint2double(n_out, oi_before); }
@@ -48,8 +45,8 @@ constexpr int kExpandAheadKernel = 4;
 constexpr int kExpandAheadTail = 8;
 
 // THE expansion: records r0, r0 + step, ... < r1 of trajectory tr, by one wavefront (lanes are samples).  Both callers -- the follow-up
-// kernel below and the solve kernel's tail (ionode_device.hpp) -- run this routine; it holds the only copy of the per-sample expressions,
-// the inline emission's (ionode_attempt_body.hpp) under the same build flags (-ffp-contract=off): same bits.
+// kernel below and the solve kernel's tail (ionode_device.hpp) -- run this routine.  The per-sample expressions are the inline emission's
+// (ionode_attempt_body.hpp): both call interp_eval / obs_current, whose single definition is in ionode_interp.hpp.
 // A record is wave-uniform: lane e < ROW loads double e of it (ONE vector load per record; a vector load also sees what the workgroup's
 // own wavefronts stored before a fence, which the scalar cache would not promise) and the fields are read out of that lane.
 // gfx9 counts loads and stores in one in-order vmcnt (ionode_device.hpp "where the dense output goes through"): a load issued behind
@@ -71,9 +68,8 @@ __device__ __forceinline__ void dense_expand_records(const KArgs &a, int tr, int
   const int last = r0 + ((r1 - 1 - r0) / step) * step;   // this wavefront's last record
   auto fetch = [&](int ri) -> double { return recs[(size_t)(ri < last ? ri : last) * Rec::ROW]; };
   struct Head {   // wave-uniform
-    double t0, den, rden;
+    Interp<S, D> itp;
     int o, n;
-    S cb[5][D];
   };
   struct Samples {   // the first lookup of a 64-sample chunk: output time, protocol index and the two protocol samples
     double tk, lo, hi;
@@ -81,13 +77,9 @@ __device__ __forceinline__ void dense_expand_records(const KArgs &a, int tr, int
     bool inr;
   };
   auto decode = [&](double raw, Head &h) {
-    h.t0 = bcast_f64(raw, Rec::T0); h.den = bcast_f64(raw, Rec::DEN); h.rden = bcast_f64(raw, Rec::RDEN);
+    h.itp.from_lane_doubles(raw);
     const double cur = bcast_f64(raw, Rec::CURSOR);
     h.o = Rec::cursor_oi(cur); h.n = Rec::cursor_n(cur);
-#pragma unroll
-    for (int c = 0; c < 5; ++c)
-#pragma unroll
-      for (int d = 0; d < D; ++d) h.cb[c][d] = (S)bcast_f64(raw, Rec::COEF + c * D + d);
   };
   auto lookup = [&](const Head &h, int c0, Samples &s) {
     s.tk = a.te_t0 + (double)(h.o + c0 + lane) * a.te_dt;
@@ -101,17 +93,8 @@ __device__ __forceinline__ void dense_expand_records(const KArgs &a, int tr, int
     const int idx = h.o + c0 + lane;
     if (c0 + lane < h.n && idx < Nt) {
       const double tk = s.tk;
-      const S x = (S)div_pos(tk - h.t0, h.den, h.rden);  // _interp_evaluate: x = (t - t0) / (t1 - t0) in fp64, cast; running powers
       S out[D];
-      S xp = x;
-#pragma unroll
-      for (int d = 0; d < D; ++d) out[d] = h.cb[0][d] + x * h.cb[1][d];
-#pragma unroll
-      for (int c = 2; c < 5; ++c) {
-        xp = xp * x;
-#pragma unroll
-        for (int d = 0; d < D; ++d) out[d] = out[d] + xp * h.cb[c][d];
-      }
+      interp_eval<S, D>(h.itp.cb, h.itp.x(tk), out);
       if (yo) {
         if constexpr (sizeof(S) == 8) {
 #pragma unroll
@@ -123,10 +106,7 @@ __device__ __forceinline__ void dense_expand_records(const KArgs &a, int tr, int
       }
       if (want_i) {
         const double vk = s.inr ? protocol_from(a, s.lo, s.hi, s.ip, tk) : a.v_oob;
-        S gate;
-        if (a.obs_open) gate = out[D - 1]; else gate = out[0] * out[1];
-        if (a.obs_g != 1.0) gate = (S)a.obs_g * gate;
-        io[idx] = (double)gate * (vk - a.obs_e);
+        io[idx] = obs_current<S, D>(a, out, vk);
       }
     }
   };

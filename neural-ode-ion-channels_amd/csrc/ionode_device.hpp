@@ -34,6 +34,7 @@
 #include "ionode_form.hpp"
 #include "ionode_kargs.hpp"   // KArgs, protocol_index / protocol_from / protocol_v
 #include "ionode_math.hpp"
+#include "ionode_interp.hpp"         // the dense-output interpolant and the observation model: the one definition
 #include "ionode_dense_expand.hpp"   // DenseRecord: what a deferring tile writes per accepted step
 
 namespace ionode {
@@ -48,10 +49,10 @@ namespace ionode {
 // gfx950 allocates LDS in 1280-byte granules; the lean 2-state kernels (<= 128 registers) want 16 wavefronts per compute unit:
 // <= 10 240 bytes, the others 12: <= 12 800.
 struct LwLds {
-  // (D, tail): model states, KernelForm::lds_key (0 general, 1 lean, 2 table).  Row stride (4 + 5 D) * 8 = 112 / 272 bytes:
+  // (D, tail): model states, KernelForm::lds_key (0 general, 1 lean, 2 table).  Row stride InterpRow<D>::BYTES = 112 / 272 bytes:
   // consecutive rows start on different LDS banks (128-byte rows put every row on the same banks: measured 30 % of the LDS
   // cycles in bank conflicts).
-  static __host__ __device__ constexpr int rowb(int D) { return (4 + 5 * D) * 8; }
+  static __host__ __device__ constexpr int rowb(int D) { return interp_row_doubles(D) * 8; }
   static __host__ __device__ constexpr int aux_off(int D) { return 64 * rowb(D); }
   static __host__ __device__ constexpr int aux_bytes(int tail) { return (tail == 1 && IONODE_LEAN) ? 0 : 64 * 64; }
   static __host__ __device__ constexpr int owp_off(int D, int tail) { return aux_off(D) + aux_bytes(tail); }
@@ -59,7 +60,6 @@ struct LwLds {
   static __host__ __device__ constexpr int clist_off(int D, int tail) { return trl_off(D, tail) + 256; }
   static __host__ __device__ constexpr int bytes(int D, int tail) { return clist_off(D, tail) + 1024; }
 };
-static_assert(LwLds::rowb(2) == DenseRecord<2>::BYTES && LwLds::rowb(6) == DenseRecord<6>::BYTES, "the deferred-output record is the lane-wise kernels' row");
 static_assert(LwLds::bytes(2, 1) <= 10240 && LwLds::bytes(2, 0) <= 12800 && LwLds::bytes(2, 2) <= 12800, "2-state kernels: 16 / 12 wavefronts per compute unit");
 
 }  // namespace ionode
@@ -270,19 +270,13 @@ __global__ void __launch_bounds__((KernelForm<MODEL, G, RT, NT, PD, TAIL>::block
     if (iout) {
       double v0;
       protocol_v(a, pv, t, v0);
-      S gate;
-      if (a.obs_open) gate = y[D - 1]; else gate = y[0] * y[1];
-      if (a.obs_g != 1.0) gate = (S)a.obs_g * gate;
-      iout[0] = (double)gate * (v0 - a.obs_e);
+      iout[0] = obs_current<S, D>(a, y, v0);
     }
   }
   if (a.sse_out != nullptr && valid) {
     double v0;
     protocol_v(a, pv, t, v0);
-    S gate;
-    if (a.obs_open) gate = y[D - 1]; else gate = y[0] * y[1];
-    if (a.obs_g != 1.0) gate = (S)a.obs_g * gate;
-    const double r0 = (double)gate * (v0 - a.obs_e) - a.sse_ref[(size_t)pidx * Nt];
+    const double r0 = obs_current<S, D>(a, y, v0) - a.sse_ref[(size_t)pidx * Nt];
     sse = r0 * r0;
   }
 

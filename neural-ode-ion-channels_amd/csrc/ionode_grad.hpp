@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "ionode_grad_step.hpp"   // GArgs and the layouts of the streams between the launches
+#include "ionode_interp.hpp"      // the forward's dense-output interpolant and observation model
 
 namespace ionode {
 
@@ -486,20 +487,55 @@ struct GradMlp {
 // state dtype: i = (double)gate(y) * (V - obs_e), r = i - ref.  Returns r and dr/dy (fp64).
 template <typename S, int D>
 __device__ __forceinline__ double sse_residual(const GArgs &a, const S (&y)[D], double v, double ref, double (&dr)[D]) {
-  S gate;
-  if (a.obs_open) gate = y[D - 1]; else gate = y[0] * y[1];
-  if (a.obs_g != 1.0) gate = (S)a.obs_g * gate;
-  const double dv = v - a.obs_e, gdv = a.obs_g * dv;
+  const double gdv = a.obs_g * (v - a.obs_e);
 #pragma unroll
   for (int d = 0; d < D; ++d) dr[d] = 0.0;
   if (a.obs_open) dr[D - 1] = gdv;
   else { dr[0] = gdv * (double)y[1]; dr[1] = gdv * (double)y[0]; }
-  return (double)gate * dv - ref;
+  return obs_current<S, D>(a, y, v) - ref;
+}
+
+// The dense-output coefficients (e, d, c, b, a) of an accepted step, fitted from its checkpoint (step length, start state, k1..k7) as
+// the forward fitted them: interp_fit in the state dtype, the same bits.  y_next: the next accepted step's checkpointed start state
+// (this step's y1), or NULL for the trajectory's last step, whose y1 is recomputed in the forward's order.
+template <typename S, int D>
+__device__ __forceinline__ void sse_fit_step(double dt, const double (&y)[D], const double (&k)[7][D], const double *__restrict__ y_next, S (&cf)[5][D]) {
+  const S dts_s = (S)dt;
+  S ys[D], y1[D], ks[7][D];
+#pragma unroll
+  for (int d = 0; d < D; ++d) ys[d] = (S)y[d];
+#pragma unroll
+  for (int jx = 0; jx < 7; ++jx)
+#pragma unroll
+    for (int d = 0; d < D; ++d) ks[jx][d] = (S)k[jx][d];
+  if (y_next) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) y1[d] = (S)y_next[d];
+  } else interp_y1<S, D>(dts_s, ys, ks, y1);
+  interp_fit_all<S, D>(dts_s, ys, y1, ks, cf);
+}
+
+// One output sample of the step: y_k from the interpolant at x (state dtype: interp_eval), its residual against `ref` at voltage
+// v, and P[c][d] += g2 r_k dr_k/dy_d x^c in fp64 (g2 = 2 dL/dsse[b]).
+template <typename S, int D>
+__device__ __forceinline__ void sse_sample_term(const GArgs &a, const S (&cf)[5][D], S xs, double v, double ref, double g2, double (&P)[5][D]) {
+  S out[D];
+  interp_eval<S, D>(cf, xs, out);
+  double dr[D];
+  const double gr = g2 * sse_residual<S, D>(a, out, v, ref, dr);
+  const double x = (double)xs;
+  double xp = 1.0;
+#pragma unroll
+  for (int c = 0; c < 5; ++c) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) P[c][d] += (gr * dr[d]) * xp;
+    xp *= x;
+  }
 }
 
 // One-phase backward sweep; SSE: the fused sum-of-squares variant (closed-form models only).  Only the source of the output
 // gradients differs: instead of reading grad_y [B][Nt][D], the sweep re-evaluates every output sample of the step from the
-// step's interpolant (fitted from the checkpoint with the forward's formula, in the state dtype: the same bits as the
+// step's interpolant (fitted from the checkpoint by the forward's own routines, ionode_interp.hpp, in the state dtype: the same bits as the
 // forward's dense output) and forms dL/dy_k = 2 dL/dsse[b] r_k dr_k/dy_k on the sample's lane.
 template <int MODEL, typename S, int NT>
 __global__ void __launch_bounds__(256) ionode_dopri5_backward_kernel(const GArgs a) {

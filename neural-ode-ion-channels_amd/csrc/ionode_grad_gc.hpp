@@ -7,86 +7,13 @@
 // chunk: the recompute kernel then runs with grad_y == NULL (it leaves the GC slots alone) and the walk takes the sample-0 term
 // from a [B][D] buffer, so no [B][Nt] array exists anywhere on the route.
 //
-// The step's dense-output fit and the per-sample term are the device functions below: the algebra of the closed-form one-phase
-// sweep (ionode_grad_sweep_body.hpp, SSE = true), which keeps its own copy (it compiles to the code it had).
+// The step's dense-output fit and the per-sample term are sse_fit_step / sse_sample_term (ionode_grad.hpp), which the closed-form
+// one-phase sweep (ionode_grad_sweep_body.hpp, SSE = true) calls too; both stand on the forward's interpolant (ionode_interp.hpp).
 #pragma once
 
 #include "ionode_grad.hpp"
 
 namespace ionode {
-
-// The dense-output coefficients (e, d, c, b, a) of an accepted step, fitted from its checkpoint record as the forward fitted them
-// (ionode_attempt_body.hpp `fit`, state dtype: the same bits).  rec1: the next accepted step's record (its y is this step's y1), or
-// NULL for the trajectory's last step, whose y1 is recomputed in the forward's order.
-template <typename S, int D>
-__device__ __forceinline__ void sse_fit_step(const double *__restrict__ rec, const double *__restrict__ rec1, S (&cf)[5][D]) {
-  using CK = CkptRecord<D>;
-  const S dts_s = (S)rec[CK::DT];
-  S ys[D], y1[D], ks[7][D];
-#pragma unroll
-  for (int d = 0; d < D; ++d) ys[d] = (S)rec[CK::Y + d];
-#pragma unroll
-  for (int jx = 0; jx < 7; ++jx)
-#pragma unroll
-    for (int d = 0; d < D; ++d) ks[jx][d] = (S)rec[CK::K + jx * D + d];
-  if (rec1) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) y1[d] = (S)rec1[CK::Y + d];
-  } else {
-    S bd[6];
-#pragma unroll
-    for (int jx = 0; jx < 6; ++jx) bd[jx] = (S)kBeta[5][jx] * dts_s;
-#pragma unroll
-    for (int d = 0; d < D; ++d) {
-      S sm = ks[0][d] * bd[0];
-#pragma unroll
-      for (int jx = 1; jx < 6; ++jx) sm = sm + ks[jx][d] * bd[jx];
-      y1[d] = ys[d] + sm;
-    }
-  }
-  S bm[7];
-#pragma unroll
-  for (int jx = 0; jx < 7; ++jx) bm[jx] = dts_s * (S)kCmid[jx];
-#pragma unroll
-  for (int d = 0; d < D; ++d) {
-    S sm = ks[0][d] * bm[0];
-#pragma unroll
-    for (int jx = 1; jx < 7; ++jx) sm = sm + ks[jx][d] * bm[jx];
-    const S YM = ys[d] + sm;
-    const S F0 = ks[0][d], F1 = ks[6][d], Y0 = ys[d], Y1 = y1[d];
-    cf[4][d] = ((S)2 * dts_s) * (F1 - F0) - (S)8 * (Y1 + Y0) + (S)16 * YM;
-    cf[3][d] = dts_s * ((S)5 * F0 - (S)3 * F1) + (S)18 * Y0 + (S)14 * Y1 - (S)32 * YM;
-    cf[2][d] = dts_s * (F1 - (S)4 * F0) - (S)11 * Y0 - (S)5 * Y1 + (S)16 * YM;
-    cf[1][d] = dts_s * F0;
-    cf[0][d] = Y0;
-  }
-}
-
-// One output sample of the step: y_k from the interpolant at x (state dtype, the forward's running powers), its residual against
-// `ref` at voltage v, and P[c][d] += g2 r_k dr_k/dy_d x^c in fp64 (g2 = 2 dL/dsse[b]).
-template <typename S, int D>
-__device__ __forceinline__ void sse_sample_term(const GArgs &a, const S (&cf)[5][D], S xs, double v, double ref, double g2, double (&P)[5][D]) {
-  S out[D];
-  S xq = xs;
-#pragma unroll
-  for (int d = 0; d < D; ++d) out[d] = cf[0][d] + xs * cf[1][d];
-#pragma unroll
-  for (int c = 2; c < 5; ++c) {
-    xq = xq * xs;
-#pragma unroll
-    for (int d = 0; d < D; ++d) out[d] = out[d] + xq * cf[c][d];
-  }
-  double dr[D];
-  const double gr = g2 * sse_residual<S, D>(a, out, v, ref, dr);
-  const double x = (double)xs;
-  double xp = 1.0;
-#pragma unroll
-  for (int c = 0; c < 5; ++c) {
-#pragma unroll
-    for (int d = 0; d < D; ++d) P[c][d] += (gr * dr[d]) * xp;
-    xp *= x;
-  }
-}
 
 constexpr int GRAD_GC_WAVES = 4;   // wavefronts (= iterations) per workgroup: grid.y stays inside HIP's 65535 for the chunks the recompute kernel takes
 
@@ -125,14 +52,21 @@ __global__ void __launch_bounds__(64 * GRAD_GC_WAVES) ionode_grad_sse_gc_kernel(
     const double t0 = rec[CK::T0], t1 = t0 + rec[CK::DT];
     const int oi = (int)rec[CK::OI], n = (int)rec[CK::NOUT];
     if (n > 0) {
+      double ys[D], ks[7][D];
+#pragma unroll
+      for (int d = 0; d < D; ++d) ys[d] = rec[CK::Y + d];
+#pragma unroll
+      for (int jx = 0; jx < 7; ++jx)
+#pragma unroll
+        for (int d = 0; d < D; ++d) ks[jx][d] = rec[CK::K + jx * D + d];
       S cf[5][D];
-      sse_fit_step<S, D>(rec, (s + 1 < nst && s + 1 < a.ckpt_cap) ? rec + RECW : nullptr, cf);
+      sse_fit_step<S, D>(rec[CK::DT], ys, ks, (s + 1 < nst && s + 1 < a.ckpt_cap) ? rec + RECW + CK::Y : nullptr, cf);
       const double den = t1 - t0, rden = 1.0 / den;   // the forward's reciprocal and div_pos: the same x bits
       for (int c0 = 0; c0 < n; c0 += 64) {
         const int idx = oi + c0 + lane;
         if (c0 + lane < n && idx >= 0 && idx < Nt) {
           const double tk = a.k.t_eval[idx];
-          const S xs = (S)div_pos(tk - t0, den, rden);
+          const S xs = interp_x<S>(tk, t0, den, rden);
           double vk;
           if (vt) vk = vt[idx];
           else protocol_v(a.k, pv, tk, vk);

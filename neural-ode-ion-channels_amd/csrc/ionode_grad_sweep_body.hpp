@@ -75,50 +75,10 @@
     const S t0s = (S)t0, dts_s = (S)dt, t1s = (S)t1;
     const double dts = (double)dts_s;
 
-    // fused objective: my step's dense-output coefficients (e, d, c, b, a), fitted as the forward fitted them (ionode_attempt_body.hpp
-    // `fit`, state dtype).  y1 is the next accepted step's checkpointed start state; the last step recomputes it as the forward did.
+    // fused objective: my step's dense-output coefficients (e, d, c, b, a), fitted as the forward fitted them (sse_fit_step).  y1 is the
+    // next accepted step's checkpointed start state; the last step recomputes it as the forward did.
     S cf[SSE ? 5 : 1][SSE ? D : 1];
-    if constexpr (SSE) {
-      S ys[D], y1[D], ks[7][D];
-#pragma unroll
-      for (int d = 0; d < D; ++d) ys[d] = (S)y[d];
-#pragma unroll
-      for (int jx = 0; jx < 7; ++jx)
-#pragma unroll
-        for (int d = 0; d < D; ++d) ks[jx][d] = (S)k[jx][d];
-      if (step && s + 1 < nst) {
-        const double *rec1 = ck + (size_t)(s + 1) * RECW;
-#pragma unroll
-        for (int d = 0; d < D; ++d) y1[d] = (S)rec1[RECY + d];
-      } else {
-        S bd[6];
-#pragma unroll
-        for (int jx = 0; jx < 6; ++jx) bd[jx] = (S)kBeta[5][jx] * dts_s;
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-          S sm = ks[0][d] * bd[0];
-#pragma unroll
-          for (int jx = 1; jx < 6; ++jx) sm = sm + ks[jx][d] * bd[jx];
-          y1[d] = ys[d] + sm;
-        }
-      }
-      S bm[7];
-#pragma unroll
-      for (int jx = 0; jx < 7; ++jx) bm[jx] = dts_s * (S)kCmid[jx];
-#pragma unroll
-      for (int d = 0; d < D; ++d) {
-        S sm = ks[0][d] * bm[0];
-#pragma unroll
-        for (int jx = 1; jx < 7; ++jx) sm = sm + ks[jx][d] * bm[jx];
-        const S YM = ys[d] + sm;
-        const S F0 = ks[0][d], F1 = ks[6][d], Y0 = ys[d], Y1 = y1[d];
-        cf[4][d] = ((S)2 * dts_s) * (F1 - F0) - (S)8 * (Y1 + Y0) + (S)16 * YM;
-        cf[3][d] = dts_s * ((S)5 * F0 - (S)3 * F1) + (S)18 * Y0 + (S)14 * Y1 - (S)32 * YM;
-        cf[2][d] = dts_s * (F1 - (S)4 * F0) - (S)11 * Y0 - (S)5 * Y1 + (S)16 * YM;
-        cf[1][d] = dts_s * F0;
-        cf[0][d] = Y0;
-      }
-    }
+    if constexpr (SSE) sse_fit_step<S, D>(dt, y, k, (step && s + 1 < nst) ? ck + (size_t)(s + 1) * RECW + RECY : nullptr, cf);
 
     // ---- adjoints of the interpolant coefficients: G_c = sum_k gy[k] * x_k^c over the step's output samples ----
 #pragma unroll
@@ -150,30 +110,10 @@
             if (c0 + lane < n) {
               const int idx = o + c0 + lane;
               const double tk = a.k.t_eval[idx];
-              const S xs = (S)div_pos(tk - t0b, den, rden);
-              S out[D];
-              S xq = xs;
-#pragma unroll
-              for (int d = 0; d < D; ++d) out[d] = cb[0][d] + xs * cb[1][d];
-#pragma unroll
-              for (int c = 2; c < 5; ++c) {
-                xq = xq * xs;
-#pragma unroll
-                for (int d = 0; d < D; ++d) out[d] = out[d] + xq * cb[c][d];
-              }
               double vk;
               if (vtb) vk = vtb[idx];
               else protocol_v(a.k, pvb, tk, vk);
-              double dr[D];
-              const double gr = g2 * sse_residual<S, D>(a, out, vk, refb[idx], dr);
-              const double x = (double)xs;
-              double xp = 1.0;
-#pragma unroll
-              for (int c = 0; c < 5; ++c) {
-#pragma unroll
-                for (int d = 0; d < D; ++d) P[c][d] += (gr * dr[d]) * xp;
-                xp *= x;
-              }
+              sse_sample_term<S, D>(a, cb, interp_x<S>(tk, t0b, den, rden), vk, refb[idx], g2, P);
             }
           }
         } else {
