@@ -195,6 +195,45 @@ int ionode_dopri5_deferred(const ionode_desc *d, const float *mlp_packed, const 
                            void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace,
                            int64_t workspace_bytes);
 
+/*
+ * Shrink-aware tile composition (since ABI 10, added later: new symbols only, ionode_desc and every earlier entry point unchanged).
+ * The lean N = 200 16-trajectory tile steps its 16 slots in lock step and finishes on the 4-trajectory net once at most 4 of them are
+ * live, so a tile takes  A5 * 6 e16 + (A1 - A5) * 6 e4  (A1, A5: largest and fifth-largest attempt count of its trajectories; e16, e4:
+ * one evaluation on either net), and a launch of at most one tile per compute unit lasts as long as its slowest tile: it depends on
+ * which trajectories share a tile.  The rule (csrc/ionode_compose.hpp): sort by cost descending, ties by index, a non-finite or
+ * negative cost counting as 0; tile k takes sorted entries 4 k .. 4 k + 3 into its slots 0 .. 3 and fills its other 12 slots from the
+ * light end, lightest first; only the last tile is ragged (the lightest heavies, at most 4, and the lights that remain); equal costs
+ * everywhere leave index order.  The result is an ionode_desc.launch_order: outputs stay at the trajectories' own indices, bit for bit.
+ *
+ * ionode_compose_plan(): out = {1 if `d` qualifies, the cost source IONODE_COMPOSE allows}.  It qualifies when ionode_dopri5 would run
+ * one of the four lean N = 200 shrink kernels (NN-f / NN-d, both state dtypes) with the shrink on (IONODE_TILE_SHRINK), with at most
+ * one tile per compute unit of the CALLER's current device (asked on every call; 256 where there is none), without traj_per_image,
+ * without a launch_order of the caller's, and n_traj <= 8192.  Source: 3 = any (default), 1 = the pilot only (IONODE_COMPOSE=pilot),
+ * 2 = an earlier call's stats only (IONODE_COMPOSE=hint), 0 = IONODE_COMPOSE=0, which also makes out[0] 0 (a development switch,
+ * read per plan).  Like ionode_dense_defer_plan it takes the protocol grid to be uniform (prot_t == NULL).
+ *
+ * ionode_compose_order(): DEVICE, asynchronous on `stream`, no host synchronisation.  Reads cost[b * cost_stride], b < n_traj, as fp64
+ * (cost_is_int64 = 0) or int64 (1: e.g. column 2 of a stats tensor in place, cost = stats + 2, cost_stride = 4) and writes
+ * order[n_traj] int32 by the rule.  One workgroup, bitonic sort in LDS; n_traj <= 8192, IONODE_ERR_UNSUPPORTED beyond.  Any cost
+ * values, garbage included, give a valid permutation.
+ *
+ * ionode_compose_order_host(): HOST -> HOST mirror of the same rule (cost fp64 [n_traj]), for tests and replays.
+ *
+ * ionode_dopri5_composed(): ionode_dopri5_deferred() for a launch whose d->launch_order came from ionode_compose_order(), plus where
+ * its cost came from -- cost_source 1: a pilot, 2: the counts of an earlier solve of the same batch (or the caller's own costs), 0 or
+ * d->launch_order == NULL: exactly ionode_dopri5_deferred().  A composed launch ends its tiles at other times than index order, so the
+ * solve kernel's tail takes its fraction of the tiles from the cost source (the rule of ionode_dense_tail_plan on the composed launch's
+ * own stamps).  Results do not depend on it.  ionode_compose_tail_plan(): ionode_dense_tail_plan() for such a launch.
+ */
+int ionode_dopri5_composed(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
+                           const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
+                           void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace,
+                           int64_t workspace_bytes, int32_t cost_source);
+int ionode_compose_tail_plan(const ionode_desc *d, int32_t want_current, int32_t cost_source, int64_t out[2]);
+int ionode_compose_plan(const ionode_desc *d, int32_t want_current, int32_t out[2]);
+int ionode_compose_order(const void *cost, int32_t cost_is_int64, int64_t cost_stride, int32_t n_traj, int32_t *order, void *stream);
+int ionode_compose_order_host(const double *cost, int32_t n_traj, int32_t *order);
+
 /* Pre-pass for ionode_desc.v_at_outputs: v_out[p][k] = V_p(t_eval[k]) for the d->n_prot protocols at the d->n_out output
  * times, by the integrator's own lookup (linear interpolation, -80 mV / v_oob outside the protocol: train-s1.py:218-237).
  * Reads d->n_out, n_prot, prot_n, prot_t0, prot_dt, v_oob.  Asynchronous on `stream`. */

@@ -32,6 +32,7 @@ EXPORTS = (
     "ionode_grad_partial_floats", "ionode_grad_reduce", "ionode_grad_reduce_unit", "ionode_grad_reduce_slabs", "ionode_grad_last_error",
     "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh", "ionode_regress_plan",
     "ionode_dense_defer_plan", "ionode_dense_tail_plan", "ionode_dopri5_deferred",
+    "ionode_compose_plan", "ionode_compose_order", "ionode_compose_order_host", "ionode_dopri5_composed", "ionode_compose_tail_plan",
 )
 
 # the backward sweep's entry points: their buffers in ABI order -- between (d, it_begin, it_end, n_iter) and stream (include/ionode.h;
@@ -123,6 +124,16 @@ def lib():
         L.ionode_dense_defer_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int64 * 2)]
         L.ionode_dense_tail_plan.restype = C.c_int
         L.ionode_dense_tail_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int64 * 2)]
+        L.ionode_compose_plan.restype = C.c_int
+        L.ionode_compose_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int32 * 2)]
+        L.ionode_compose_order.restype = C.c_int
+        L.ionode_compose_order.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
+        L.ionode_dopri5_composed.restype = C.c_int
+        L.ionode_dopri5_composed.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 13 + [C.c_int64, C.c_int32]
+        L.ionode_compose_tail_plan.restype = C.c_int
+        L.ionode_compose_tail_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.POINTER(C.c_int64 * 2)]
+        L.ionode_compose_order_host.restype = C.c_int
+        L.ionode_compose_order_host.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
         L.ionode_grad_last_error.restype = C.c_char_p
         for fn in (L.ionode_grad_image_floats, L.ionode_grad_record_floats, L.ionode_grad_partial_floats):
             fn.restype = C.c_size_t
@@ -233,6 +244,55 @@ def dense_tail_plan(desc, want_current):
     return {"tail_rank": int(out[0]), "usable_capacity": int(out[1])}
 
 
+COST_SOURCE = {None: 0, "pilot": 1, "hint": 2, "explicit": 2}   # ionode_dopri5_composed's cost_source of dopri5()["composed"]
+COMPOSE_SOURCES = {0: "off", 1: "pilot", 2: "hint", 3: "auto"}
+# the pilot of the tile composition: HH 2-state on the same protocols (schedule.pilot_cost's model).  A loose tolerance ranks the
+# trajectories as well as the solve's own (composed maximum 313.7 ms at 1e-4 / 1e-6 against 313.3 at 1e-7 / 1e-9) at 40 % of the attempts
+PILOT_RTOL, PILOT_ATOL = 1e-4, 1e-6
+PILOT_MAX_ATTEMPTS = 100000   # runaway bound of a pilot trajectory (the headline's take about 1100): it then simply ranks heaviest
+
+
+def compose_plan(desc, want_current):
+    """Shrink-aware tile composition (ionode_compose_plan): does `desc` qualify, and which cost source IONODE_COMPOSE allows."""
+    out = (C.c_int32 * 2)()
+    if lib().ionode_compose_plan(C.byref(desc), int(bool(want_current)), C.byref(out)) != 0:
+        raise IonodeError(last_error())
+    return {"compose": bool(out[0]), "source": COMPOSE_SOURCES[int(out[1])]}
+
+
+def compose_tail_plan(desc, want_current, composed):
+    """dense_tail_plan for a launch composed from `composed` (dopri5()["composed"]: None, "pilot", "hint", "explicit")."""
+    out = (C.c_int64 * 2)()
+    if lib().ionode_compose_tail_plan(C.byref(desc), int(bool(want_current)), COST_SOURCE[composed], C.byref(out)) != 0:
+        raise IonodeError(last_error())
+    return {"tail_rank": int(out[0]), "usable_capacity": int(out[1])}
+
+
+def compose_order_host(cost):
+    """The composition rule on the host (ionode_compose_order_host): cost [B] -> int32 launch order [B], numpy."""
+    c = np.ascontiguousarray(np.asarray(cost, dtype=np.float64).reshape(-1))
+    order = np.empty(c.size, dtype=np.int32)
+    if lib().ionode_compose_order_host(c.ctypes.data, int(c.size), order.ctypes.data) != 0:
+        raise IonodeError(last_error())
+    return order
+
+
+def compose_order(cost, stream=None):
+    """The composition rule on the device (ionode_compose_order), asynchronous on the current stream: cost is a 1-D fp64 or int64
+    device tensor of any stride (a column of a stats tensor is read in place) -> int32 launch order [B]."""
+    if not isinstance(cost, torch.Tensor) or not cost.is_cuda or cost.dim() != 1 or cost.dtype not in (torch.float64, torch.int64) \
+            or cost.shape[0] < 1 or (cost.shape[0] > 1 and cost.stride(0) < 1):
+        raise IonodeError("cost: expected a 1-D float64 or int64 CUDA/HIP tensor with a positive stride")
+    B = int(cost.shape[0])
+    order = torch.empty((B,), dtype=torch.int32, device=cost.device)
+    s = stream if stream is not None else torch.cuda.current_stream(cost.device).cuda_stream
+    rc = lib().ionode_compose_order(C.c_void_p(cost.data_ptr()), int(cost.dtype == torch.int64), max(1, int(cost.stride(0))), B,
+                                    C.c_void_p(order.data_ptr()), C.c_void_p(s))
+    if rc != 0:
+        raise IonodeError(f"ionode_compose_order failed ({rc}): {last_error()}")
+    return order
+
+
 def kernel_name(desc):
     return lib().ionode_kernel_name(C.byref(desc)).decode()
 
@@ -280,13 +340,22 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
            prot_t0=0.0, prot_dt=1.0, prot_of_traj=None, rtol=1e-7, atol=1e-9, v_oob=-80.0, max_steps=0,
            max_total_steps=0, max_step=0.0, ckpt=None, current=False, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False, tile_waves=0, stats=True,
            step_log=None, t_eval_hint="auto", t_eval_exact=None, sse_ref=None, states=True, out=None, stream=None,
-           v_at_outputs="auto", traj_per_image=0, launch_order="auto", workspace=None):
+           v_at_outputs="auto", traj_per_image=0, launch_order="auto", workspace=None, cost_hint="auto"):
     """Launch one batched solve.  Every tensor lives on the current HIP device.
 
     launch_order: None (index order), an int32 device permutation [B] (ionode_desc.launch_order: slot s integrates trajectory
     order[s]; results stay at the trajectories' own indices, bit-identical to index order), or "auto": protocol-major order for
     the one-trajectory-per-lane kernels when several protocols are interleaved (the 64 lanes of a wavefront then interpolate
     one protocol instead of 64: -5 % on 393 216 HH trajectories over 64 protocols).
+
+    cost_hint: where launch_order="auto" takes the cost of the shrink-aware tile composition from, when compose_plan() says the launch
+    qualifies (the lean N = 200 16-tile at one tile per compute unit; 4 heaviest + 12 lightest per tile, ionode_compose_order): a 1-D
+    fp64 / int64 device tensor [B] gives explicit costs, None composes nothing, "auto" (default) reads the RHS evaluations of an
+    earlier call from the `stats` tensor that `out=` carries (a training loop re-solves the same batch with slowly changing weights)
+    and otherwise runs a pilot first -- the HH 2-state model on the same protocols, two output times, loose tolerance.  "hint" and
+    "pilot" ask for one of the two by name; "auto" composes only the dispatcher's own 16-tile (tile_waves = 0), the others also a
+    forced one.  A stale or wrong cost changes the time, never the results.  IONODE_COMPOSE=0|pilot|hint in the environment
+    restricts the source.
 
     workspace: optional uint8 device tensor for the deferred dense output (at least dense_defer_plan's bytes, 16-byte aligned) instead
     of one from torch's allocator -- a caller that wants to read the record counts back (tests) keeps it.
@@ -324,7 +393,8 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
             k = torch.arange(Nt, dtype=torch.float64, device=t_eval.device)
             t_eval_exact = bool(torch.equal(t_eval, float(t_eval_hint[0]) + k * float(t_eval_hint[1])))
         desc.t_eval_exact = int(bool(t_eval_exact))
-    if isinstance(launch_order, str):
+    auto_order = isinstance(launch_order, str)
+    if auto_order:
         if launch_order != "auto":
             raise IonodeError("launch_order: None, 'auto' or an int32 device tensor [B]")
         launch_order = None
@@ -366,6 +436,7 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
     if status is None:
         status = torch.empty((B,), dtype=torch.int32, device=dev)
     st = out.get("stats")
+    stats_from_caller = st is not None
     if stats and st is None:
         st = torch.empty((B, 4), dtype=torch.int64, device=dev)
     s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
@@ -381,6 +452,32 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
             _dev_ptr(vtab, torch.float64, "v_at_outputs", (P, Nt))
         if vtab is not None:
             desc.v_at_outputs = vtab.data_ptr()
+    # shrink-aware tile composition: an order made on the device, on this stream, ahead of the solve.  Its buffers come from torch's
+    # caching allocator like the record workspace below, so a foreign stream composes nothing
+    composed = None
+    if auto_order and launch_order is None and cost_hint is not None and stream is None and prot_t is None and Nt >= 2:
+        cp = compose_plan(desc, i_out is not None)
+        if cp["compose"]:
+            # "auto" follows the dispatcher's own choice of the tile only: a forced tile_waves pins the schedule (tuning runs and tests
+            # that read per-tile effects back rely on index tiles); "pilot" / "hint" / a tensor ask for the composition explicitly
+            want = cost_hint if not (isinstance(cost_hint, str) and cost_hint == "auto" and tile_waves) else None
+            cost = None
+            if isinstance(want, torch.Tensor):
+                if tuple(want.shape) != (B,):
+                    raise IonodeError(f"cost_hint: expected shape {(B,)}, got {tuple(want.shape)}")
+                cost, composed = want, "explicit"
+            elif want is not None and want not in ("auto", "pilot", "hint"):
+                raise IonodeError("cost_hint: None, 'auto', 'pilot', 'hint' or a device tensor [B]")
+            elif want in ("auto", "hint") and cp["source"] in ("hint", "auto") and stats_from_caller and _dev_ptr(st, torch.int64, "stats", (B, 4)):
+                cost, composed = st[:, 2], "hint"
+            elif want in ("auto", "pilot") and cp["source"] in ("pilot", "auto"):
+                pilot = dopri5(MODEL_HH2, params, prot_v, y0, torch.stack((t_eval[0], t_eval[Nt - 1])), prot_t0=prot_t0, prot_dt=prot_dt,
+                               prot_of_traj=prot_of_traj, rtol=PILOT_RTOL, atol=PILOT_ATOL, v_oob=v_oob, t_eval_hint=None,
+                               max_total_steps=PILOT_MAX_ATTEMPTS, launch_order=None, cost_hint=None)
+                cost, composed = pilot["stats"][:, 2], "pilot"
+            if cost is not None:
+                launch_order = compose_order(cost)
+                desc.launch_order = launch_order.data_ptr()
     # deferred dense output: the record workspace comes from torch's caching allocator (repeat calls cost nothing) and goes back to it
     # when this call returns -- in stream order, which holds for torch's current stream only, so a foreign stream defers nothing
     ws = None
@@ -392,7 +489,7 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
                 if workspace.numel() < plan["workspace_bytes"]:
                     raise IonodeError(f"workspace: {workspace.numel()} bytes, the plan asks for {plan['workspace_bytes']}")
             ws = workspace if workspace is not None else torch.empty((plan["workspace_bytes"],), dtype=torch.uint8, device=dev)
-    rc = lib().ionode_dopri5_deferred(
+    rc = lib().ionode_dopri5_composed(
         C.byref(desc),
         _dev_ptr(mlp_packed, torch.float32, "mlp_packed"),
         _dev_ptr(params, torch.float64, "params", (B, params.shape[1])),
@@ -408,11 +505,12 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
         C.c_void_p(s),
         C.c_void_p(ws.data_ptr()) if ws is not None else None,
         ws.numel() if ws is not None else 0,
+        COST_SOURCE[composed],
     )
     if rc != 0:
         raise IonodeError(f"ionode_dopri5 failed ({rc}): {last_error()}")
     return {"y": y, "i": i_out, "status": status, "stats": st, "sse": sse, "desc": desc, "v_at_outputs": vtab,
-            "kernel": lib().ionode_last_kernel_name().decode()}
+            "launch_order": launch_order, "composed": composed, "kernel": lib().ionode_last_kernel_name().decode()}
 
 
 def uniform_grid(t_eval):

@@ -7,6 +7,7 @@
 #include <cstring>
 #include <vector>
 
+#include "ionode_compose.hpp"
 #include "ionode_launch.hpp"
 
 namespace {
@@ -237,16 +238,22 @@ DeferPlan plan_defer(const ionode_desc *d, const Plan &pl, bool want_i) {
 // The finish counter lives in the workspace's last record slot, so with the tail on a trajectory fills cap - 1 records (the stride and
 // the workspace stay what ionode_dense_defer_plan reports).  IONODE_DEFER_TAIL=0: no tile, IONODE_DEFER_TAIL=all: every tile,
 // IONODE_DEFER_TAIL_RANK=n: n tiles (dev overrides for A/B runs and tests, read per plan like IONODE_TILE_SHRINK).
+// A composed launch (ionode_compose.hpp) ends its tiles at other times -- 255 of the headline's 256 within 10 ms of each other, the
+// heaviest trajectory's tile 10 ms later -- so the fraction is a constant per cost source (ionode_dopri5_composed).  The rule's factor
+// of two gives 0/8 and 1/8 there; the bench at 5/8 and 6/8 shows the in-kernel expansions still hidden (one expansion's margin), so all
+// three are 5 (profiles/compose_order.md).
 constexpr int64_t kDeferTailEighths = 5;
+constexpr int64_t kDeferTailEighthsPilot = 5;
+constexpr int64_t kDeferTailEighthsCounts = 5;
 struct TailPlan {
   int64_t rank = 0, fill = 0;
 };
-TailPlan plan_tail(const Plan &pl, const DeferPlan &dp) {
+TailPlan plan_tail(const Plan &pl, const DeferPlan &dp, int cost_source = 0) {
   TailPlan t;
   t.fill = dp.cap;
   if (dp.cap < 2) return t;
   const int64_t tiles = (int64_t)pl.grid;
-  t.rank = tiles * kDeferTailEighths / 8;
+  t.rank = tiles * (cost_source == 1 ? kDeferTailEighthsPilot : cost_source == 2 ? kDeferTailEighthsCounts : kDeferTailEighths) / 8;
   const char *fr = getenv("IONODE_DEFER_TAIL_RANK");
   if (fr != nullptr && fr[0] != '\0') t.rank = std::max<int64_t>(0, std::min<int64_t>(atoll(fr), tiles));
   const char *sw = getenv("IONODE_DEFER_TAIL");
@@ -256,6 +263,34 @@ TailPlan plan_tail(const Plan &pl, const DeferPlan &dp) {
   }
   if (t.rank > 0) t.fill = dp.cap - 1;
   return t;
+}
+
+// Shrink-aware tile composition (ionode_compose.hpp): a launch qualifies when it runs one of the four lean N = 200 shrink kernels with
+// the shrink on, has at most one tile per compute unit (then every tile starts at once and the launch is as long as its slowest tile),
+// no traj_per_image (a tile reads one image) and no order of the caller's.  IONODE_COMPOSE=0|pilot|hint selects where the cost may
+// come from (dev override for A/B runs, read per plan like IONODE_TILE_SHRINK): 0 composes nothing, pilot always runs the pilot, hint
+// only ever reads an earlier call's stats.
+enum ComposeSource : int32_t { kComposeOff = 0, kComposePilot = 1, kComposeHint = 2, kComposeAuto = 3 };
+ComposeSource compose_source() {
+  const char *sw = getenv("IONODE_COMPOSE");
+  if (sw == nullptr || sw[0] == '\0') return kComposeAuto;
+  if (strcmp(sw, "pilot") == 0) return kComposePilot;
+  if (strcmp(sw, "hint") == 0) return kComposeHint;
+  return atoi(sw) == 0 ? kComposeOff : kComposeAuto;
+}
+// compute units of the CALLER's current device, asked on every plan (a process may drive several devices, or partitions of one);
+// 256 -- an unpartitioned MI355X -- where there is no device (plans are also computed on hosts without a GPU)
+int compute_units_now() {
+  int dev = 0, n = 0;
+  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1) {
+    (void)hipGetLastError();
+    return 256;
+  }
+  return n;
+}
+bool plan_compose(const ionode_desc *d, const Plan &pl) {
+  return pl.v->shrink && pl.tile_shrink && pl.v->traj_per_tile == ionode::kComposeTile && d->traj_per_image <= 0 &&
+         d->launch_order == nullptr && d->n_traj <= ionode::kComposeMaxB && (int64_t)pl.grid <= (int64_t)compute_units_now();
 }
 
 int make_plan(const ionode_desc *d, Plan *pl, bool want_current = false, bool explicit_grid = false) {
@@ -582,6 +617,55 @@ int ionode_dense_tail_plan(const ionode_desc *d, int32_t want_current, int64_t o
   return IONODE_OK;
 }
 
+
+int ionode_compose_tail_plan(const ionode_desc *d, int32_t want_current, int32_t cost_source, int64_t out[2]) {
+  Plan pl;
+  const int rc = make_plan(d, &pl, want_current != 0 || (d && d->sse_out != nullptr));
+  if (rc != IONODE_OK) return rc;
+  if (cost_source < 0 || cost_source > 2) { set_err("cost_source: 0 (not composed), 1 (pilot) or 2 (counts)"); return IONODE_ERR_ARG; }
+  const TailPlan tp = plan_tail(pl, plan_defer(d, pl, want_current != 0), d->launch_order ? cost_source : 0);
+  out[0] = tp.rank;
+  out[1] = tp.fill;
+  return IONODE_OK;
+}
+
+int ionode_compose_plan(const ionode_desc *d, int32_t want_current, int32_t out[2]) {
+  Plan pl;
+  const int rc = make_plan(d, &pl, want_current != 0 || (d && d->sse_out != nullptr));
+  if (rc != IONODE_OK) return rc;
+  const ComposeSource src = compose_source();
+  out[0] = (src != kComposeOff && plan_compose(d, pl)) ? 1 : 0;
+  out[1] = (int32_t)src;
+  return IONODE_OK;
+}
+
+int ionode_compose_order_host(const double *cost, int32_t n_traj, int32_t *order) {
+  if (!cost || !order || n_traj < 1) { set_err("ionode_compose_order_host: bad argument"); return IONODE_ERR_ARG; }
+  std::vector<int32_t> idx((size_t)n_traj);
+  std::vector<double> c((size_t)n_traj);
+  for (int32_t i = 0; i < n_traj; ++i) { idx[i] = i; c[i] = ionode::compose_cost(cost[i]); }
+  std::sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) { return ionode::compose_before(c[x], x, c[y], y); });
+  const bool flat = c[idx[0]] == c[idx[n_traj - 1]];
+  for (int32_t p = 0; p < n_traj; ++p) order[flat ? p : ionode::compose_slot(p, n_traj)] = idx[p];
+  return IONODE_OK;
+}
+
+int ionode_compose_order(const void *cost, int32_t cost_is_int64, int64_t cost_stride, int32_t n_traj, int32_t *order, void *stream) {
+  if (!cost || !order || n_traj < 1 || cost_stride < 1) { set_err("ionode_compose_order: bad argument"); return IONODE_ERR_ARG; }
+  if (n_traj > ionode::kComposeMaxB) { set_err("ionode_compose_order: more trajectories than the one-workgroup sort holds (8192)"); return IONODE_ERR_UNSUPPORTED; }
+  const size_t lds = ionode::compose_lds_bytes(n_traj);
+  auto kern = cost_is_int64 ? ionode::ionode_compose_kernel<1> : ionode::ionode_compose_kernel<0>;
+  if (lds > 64 * 1024) {
+    const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (ea != hipSuccess) { set_err("kernel launch failed: %s", hipGetErrorString(ea)); return IONODE_ERR_LAUNCH; }
+  }
+  hipLaunchKernelGGL(kern, dim3(1), dim3(ionode::kComposeThreads), lds, reinterpret_cast<hipStream_t>(stream), cost, (long long)cost_stride,
+                     (int)n_traj, order);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_err("kernel launch failed: %s", hipGetErrorString(e)); return IONODE_ERR_LAUNCH; }
+  return IONODE_OK;
+}
+
 }  // extern "C"
 
 namespace {
@@ -589,7 +673,8 @@ namespace {
 // ionode_dopri5 and ionode_dopri5_deferred: the solve and, when the plan defers the dense output into `workspace`, its expansion
 int dopri5_impl(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
                 const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
-                void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace, int64_t workspace_bytes) {
+                void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace, int64_t workspace_bytes,
+                int cost_source = 0) {
   Plan pl;
   const int rc = make_plan(d, &pl, i_out != nullptr || d->sse_out != nullptr, prot_t != nullptr);
   if (rc != IONODE_OK) return rc;
@@ -640,7 +725,7 @@ int dopri5_impl(const ionode_desc *d, const float *mlp_packed, const double *par
     a.defer_count = static_cast<int32_t *>(workspace);
     a.defer_rec = reinterpret_cast<double *>(static_cast<unsigned char *>(workspace) + ionode::DenseRecord<2>::records_offset(d->n_traj));
     a.defer_cap = (int32_t)dp.cap;
-    const TailPlan tp = plan_tail(pl, dp);
+    const TailPlan tp = plan_tail(pl, dp, d->launch_order ? cost_source : 0);
     a.defer_fill = (int32_t)tp.fill;
     a.defer_tail_rank = (int32_t)tp.rank;
     if (tp.rank > 0) {
@@ -680,6 +765,15 @@ int ionode_dopri5_deferred(const ionode_desc *d, const float *mlp_packed, const 
                            int64_t workspace_bytes) {
   return dopri5_impl(d, mlp_packed, params, prot_v, prot_t, prot_of_traj, y0, t_eval, y_out, i_out, status, stats, stream, workspace,
                      workspace_bytes);
+}
+
+int ionode_dopri5_composed(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
+                           const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
+                           void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace,
+                           int64_t workspace_bytes, int32_t cost_source) {
+  if (cost_source < 0 || cost_source > 2) { set_err("cost_source: 0 (not composed), 1 (pilot) or 2 (counts)"); return IONODE_ERR_ARG; }
+  return dopri5_impl(d, mlp_packed, params, prot_v, prot_t, prot_of_traj, y0, t_eval, y_out, i_out, status, stats, stream, workspace,
+                     workspace_bytes, cost_source);
 }
 
 int ionode_protocol_at_outputs(const ionode_desc *d, const double *prot_v, const double *prot_t, const double *t_eval,

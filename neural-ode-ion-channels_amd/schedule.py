@@ -4,9 +4,19 @@ A tile integrates its 16 trajectories in lock step until the slowest one finishe
 workgroups to compute units in grid order as units free up.  So the launch order decides two things: how much of a tile's
 time is spent on lanes that have already finished (tile-max over tile-mean NFE, ~9 % with an arbitrary order), and how long
 the last tiles run alone at the end of the launch.  Sorting the trajectories by predicted cost, most expensive first,
-makes tiles homogeneous and turns the dispatcher into a longest-processing-time-first list scheduler.  With one tile per
-compute unit (B = 16 x 256 = 4096) the launch is as long as its slowest trajectory whatever the order; the order pays
-from two tiles per unit upwards (BASELINE configs[2], [3]).
+makes tiles homogeneous and turns the dispatcher into a longest-processing-time-first list scheduler; that pays from two
+tiles per unit upwards (BASELINE configs[2], [3]).
+
+With one tile per compute unit (B = 16 x 256 = 4096) every tile starts at once and the launch is as long as its slowest TILE.
+Before the tile shrink that was the slowest trajectory whatever the order.  Since the lean N = 200 16-tile finishes on the
+4-trajectory net once <= 4 of its trajectories are live (MlpShrink4), a tile takes  A5 * 6 e16 + (A1 - A5) * 6 e4  (A1, A5:
+largest and fifth-largest attempt count of its trajectories; e4 / e16 = 24.3 k / 34.08 k cycles per evaluation), so it is slow
+when its FIFTH trajectory is slow -- in index order, luck.  There homogeneous tiles are the wrong goal: the composition that
+works puts the 4 heaviest trajectories with the 12 lightest, the next 4 with the next 12, and so on, which bounds the launch
+by the single heaviest trajectory on the small net (headline replay 323.4 -> 309.3 ms with exact costs).  That
+rule lives in the library (csrc/ionode_compose.hpp, ionode_compose_order) and `capi.dopri5(launch_order="auto")` applies it by
+itself -- cost from the `stats` of an earlier call carried in `out=`, else from a pilot as `pilot_cost` below runs it -- so
+nothing here needs to be called for it; `lpt_order` stays the order for launches of several tiles per unit.
 
 The reference has no counterpart: it solves one trajectory per `odeint` call (train-s1.py:566-580).  SURVEY.md 8(e)
 asks for protocol-binned sharding; `lpt_order` of a per-protocol cost gives exactly that as a special case.

@@ -26,6 +26,9 @@ def main():
     ap.add_argument("--batch", type=int, default=4096)
     ap.add_argument("--nt", type=int, default=100001)
     ap.add_argument("--uniform-scale", action="store_true", help="one protocol scale set for every trajectory: all tiles end together")
+    ap.add_argument("--compose", choices=("none", "exact", "pilot"), default="none",
+                    help="tile composition of the stamped launch (capi.dopri5 cost_hint): index order, the RHS evaluations of a first "
+                         "solve of the same batch as cost, or the pilot")
     args = ap.parse_args()
     import bench
     ion = importlib.import_module("neural-ode-ion-channels_amd")
@@ -45,13 +48,19 @@ def main():
     tiles = (B + 15) // 16
     rows = (64 + 4 * tiles + 3) // 4
     slog = torch.zeros((rows, 4), dtype=torch.float64, device=dev)
-    r = capi.dopri5(capi.MODEL_NNF, params, pv, y0, te, mlp_packed=packed, mlp_layers=bench.MLP_L, mlp_width=bench.MLP_N,
-                    prot_t0=0.0, prot_dt=0.1, current=True, tile_waves=4, t_eval_hint=(0.0, 0.1), step_log=slog)
+    kw = dict(mlp_packed=packed, mlp_layers=bench.MLP_L, mlp_width=bench.MLP_N, prot_t0=0.0, prot_dt=0.1, current=True, tile_waves=4,
+              t_eval_hint=(0.0, 0.1))
+    hint = {"none": None, "exact": "hint", "pilot": "pilot"}[args.compose]
+    prev = {}
+    if args.compose == "exact":
+        first = capi.dopri5(capi.MODEL_NNF, params, pv, y0, te, step_log=torch.zeros_like(slog), cost_hint=None, **kw)
+        prev = {k: first[k] for k in ("y", "i", "status", "stats")}
+    r = capi.dopri5(capi.MODEL_NNF, params, pv, y0, te, step_log=slog, cost_hint=hint, out=prev, **kw)
     torch.cuda.synchronize()
     s = slog.cpu().numpy().reshape(-1)[64 + tiles:64 + 4 * tiles].reshape(tiles, 3)
-    tail = capi.dense_tail_plan(r["desc"], True)
+    tail = capi.compose_tail_plan(r["desc"], True, r["composed"])
     out = {"kernel": capi.lib().ionode_last_kernel_name().decode(), "tiles": tiles, "tail": tail,
-           "switch": os.environ.get("IONODE_DEFER_TAIL", "default")}
+           "switch": os.environ.get("IONODE_DEFER_TAIL", "default"), "compose": args.compose, "composed": r["composed"]}
     if s[:, 0].max() > 0:
         ms = lambda ticks: ticks / 1e5   # 100 MHz
         t0 = s[:, 0].min()
