@@ -34,7 +34,10 @@ __device__ constexpr double kCmid[7] = {
 
 // Deterministic exp() and fifth root (DESIGN.md "Deterministic transcendentals"): dopri5's controller
 // amplifies last-ulp differences of these two functions chaotically, so results are only reproducible
-// across devices/libraries if both are fixed IEEE operation sequences.  < 1 ulp / <= 2 ulp accurate.
+// across devices/libraries if both are fixed IEEE operation sequences.  < 1 ulp / <= 2 ulp accurate: det_exp over its whole
+// domain, subnormal results (in units of 2^-1074) and both edges included; det_root5 for NORMAL x -- for subnormal x seven Newton steps
+// from the exponent-field guess do not converge (det_root5(5e-324) = 5.5e-63 for 2.2e-65; harmless, the controller clamps the
+// factor), there it only equals the oracle's.  tests/test_gpu_math_probe.py checks every function of this header on the device.
 __device__ __forceinline__ double pow2i(int k) { return __longlong_as_double((long long)(k + 1023) << 52); }
 
 // fma(p, r, c) with the constant c as a SCALAR operand.  Left to itself hipcc emits v_fmac_f64 with c copied into the destination
@@ -179,7 +182,8 @@ __device__ __forceinline__ double div_pos(double a, double b, double rb) {
 
 // a / b for a compile-time constant b (rb = RN(1 / b)): the same correction step, with the true division kept for the quotients
 // the proof excludes (zero, subnormal range, overflow).  fp32: checked against x / 1000.0f for all 2^32 inputs -- they differ only
-// where |quotient| < 2^-126 (67 108 inputs, all |x| < 9.5e-38); the guards below are far inside the safe range.
+// where |quotient| < 2^-126 (67 108 inputs, all |x| < 9.5e-38); the guards below are far inside the safe range
+// (tests/test_gpu_math_probe.py runs that sweep with the guards in place: no input differs).
 __device__ __forceinline__ double div_const(double a, double b, double rb) {
   const double q0 = a * rb;
   const double r = fma(-b, q0, a);
