@@ -100,7 +100,8 @@ typedef struct ionode_desc {
                           written to sse_out[b] (inf where the solve failed -- the reference's time-limit rule); y_out and i_out
                           may then be NULL, so that no trace leaves the chip: BASELINE configs[3]'s 65 536 candidates x 32
                           sweeps x 1e5 samples would be 4.5 TB of traces.  Needs the output-grid hint. */
-  double *sse_out;     /* DEVICE [n_traj] fp64 or NULL */
+  double *sse_out;     /* DEVICE [n_traj] fp64 or NULL.  Through ionode_dopri5_objective(IONODE_OBJECTIVE_SAE) the sums are of
+                          |i_k - sse_ref[protocol][k]| instead (both fields keep their names) */
   double max_step;     /* EXTENSION (torchdiffeq 0.2.1's dopri5 has no such option; 0 = off = reference behaviour): cap on the
                           step size in ms.  At an equilibrium dopri5 grows dt until h*lambda leaves its stability region
                           (the error estimate of a state AT equilibrium is ~0); the forward solve copes through rejections,
@@ -233,6 +234,31 @@ int ionode_compose_tail_plan(const ionode_desc *d, int32_t want_current, int32_t
 int ionode_compose_plan(const ionode_desc *d, int32_t want_current, int32_t out[2]);
 int ionode_compose_order(const void *cost, int32_t cost_is_int64, int64_t cost_stride, int32_t n_traj, int32_t *order, void *stream);
 int ionode_compose_order_host(const double *cost, int32_t n_traj, int32_t *order);
+
+/*
+ * The kind of the fused objective (since ABI 10, added later: new symbols only, ionode_desc and every earlier entry point unchanged).
+ * What a trajectory's samples add to d->sse_out[b], against d->sse_ref (the field names stay, whatever the kind):
+ *   IONODE_OBJECTIVE_SSE  sum_k (i_k - sse_ref[protocol][k])^2 -- what sse_out has always held (PINTS SumOfSquaresError);
+ *   IONODE_OBJECTIVE_SAE  sum_k |i_k - sse_ref[protocol][k]| -- n_out times the reference's prediction loss
+ *                         torch.mean(torch.abs(pred_yo - data)) (train-s1.py:275-353, the validation of train-r1.py:930-959), which it
+ *                         only ever evaluates under torch.no_grad(): a forward quantity, the backward entry points do not know it.
+ * Same kernels, same summation order, same inf for a failed trajectory: the kind is a wave-uniform kernel argument that selects the
+ * term a residual contributes (csrc/ionode_interp.hpp residual_term), and with IONODE_OBJECTIVE_SSE every output is bit for bit what
+ * the earlier entry points write.  One exception in the choice of kernel, none in the results: the lean N = 200 16-trajectory tile
+ * kernels (the ones that shrink and defer) fill the register file and are compiled for the squares alone, so IONODE_OBJECTIVE_SAE on
+ * that tile runs its general variant.
+ *
+ * ionode_dopri5_objective(): ionode_dopri5_composed() plus `objective`.  IONODE_OBJECTIVE_SSE is exactly ionode_dopri5_composed().
+ * IONODE_OBJECTIVE_SAE needs d->sse_out (and, as every fused objective, d->sse_ref and the output-grid hint; nothing is deferred).
+ * IONODE_ERR_ARG, checked before any other argument and before any launch, for another value of `objective` and for
+ * IONODE_OBJECTIVE_SAE without d->sse_out.
+ */
+#define IONODE_OBJECTIVE_SSE 0
+#define IONODE_OBJECTIVE_SAE 1
+int ionode_dopri5_objective(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
+                            const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
+                            void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace,
+                            int64_t workspace_bytes, int32_t cost_source, int32_t objective);
 
 /* Pre-pass for ionode_desc.v_at_outputs: v_out[p][k] = V_p(t_eval[k]) for the d->n_prot protocols at the d->n_out output
  * times, by the integrator's own lookup (linear interpolation, -80 mV / v_oob outside the protocol: train-s1.py:218-237).

@@ -68,6 +68,7 @@ class Solution:
     stats: Optional[torch.Tensor]   # [B, 4] int64: accepted, rejected, nfe, status
     kernel: str
     sse: Optional[torch.Tensor] = None  # [B] fp64 fused sum of squared current residuals (sse_ref given), inf where failed
+    sae: Optional[torch.Tensor] = None  # [B] fp64 fused sum of absolute current residuals (sse_ref given, objective="sae"; sse is then None)
     order: Optional[torch.Tensor] = None  # [B] int64 launch order (solve(order=...)): row k of every field is trajectory order[k]
 
     def to_original(self, x):
@@ -91,7 +92,7 @@ def solve(model, params, prot_v, y0, t_eval, *, weights=None, mlp_layers=0, mlp_
           prot_t=None, prot_t0=0.0, prot_dt=1.0, prot_of_traj=None, state_dtype=None, rtol=1e-7, atol=1e-9,
           v_oob=-80.0, max_steps=0, max_total_steps=0, max_step=0.0, current=False, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False,
           tile_waves=0, device=None, step_log=None, t_eval_hint="auto", prot_key=None, t_eval_key=None, sse_ref=None,
-          states=True, order=None, traj_per_image=0, launch_order="auto", cost_hint="auto") -> Solution:
+          states=True, order=None, traj_per_image=0, launch_order="auto", cost_hint="auto", objective="sse") -> Solution:
     """Integrate B trajectories on the GPU (asynchronous on the current stream).
 
     params [B, 8|12] (or [8|12] -> B = 1), prot_v [P, Np] (or [Np]), y0 [B, D] / [D] (broadcast over B),
@@ -109,6 +110,8 @@ def solve(model, params, prot_v, y0, t_eval, *, weights=None, mlp_layers=0, mlp_
     (cost_hint: capi.dopri5), index order otherwise; None: index order.  Not combined with `order` or traj_per_image.
     traj_per_image: with `weights` [n_sets, n] (an ensemble of trained nets, a population of initialisations): trajectory b is
     integrated with weight set b // traj_per_image (a multiple of 16); not combined with `order`.
+    objective: what sse_ref accumulates per trajectory -- "sse" (default, Solution.sse: squared residuals) or "sae" (Solution.sae:
+    absolute residuals, Nt times the reference's torch.mean(torch.abs(pred_yo - data))); capi.dopri5.
     """
     dev = _dev(device)
     t_eval_exact = None
@@ -180,6 +183,6 @@ def solve(model, params, prot_v, y0, t_eval, *, weights=None, mlp_layers=0, mlp_
                     max_steps=max_steps, max_total_steps=max_total_steps, max_step=max_step, current=current, obs_g=obs_g, obs_e=obs_e,
                     obs_open_state_only=obs_open_state_only, tile_waves=tile_waves, step_log=step_log,
                     t_eval_hint=t_eval_hint, t_eval_exact=t_eval_exact, sse_ref=_to(sse_ref, torch.float64, dev), states=states,
-                    launch_order=launch_order, cost_hint=cost_hint)
-    return Solution(y=r["y"], i=r["i"], status=r["status"], stats=r["stats"], kernel=r["kernel"], sse=r["sse"],
+                    launch_order=launch_order, cost_hint=cost_hint, objective=objective)
+    return Solution(y=r["y"], i=r["i"], status=r["status"], stats=r["stats"], kernel=r["kernel"], sse=r["sse"], sae=r["sae"],
                     order=order_t)

@@ -33,7 +33,12 @@ EXPORTS = (
     "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh", "ionode_regress_plan",
     "ionode_dense_defer_plan", "ionode_dense_tail_plan", "ionode_dopri5_deferred",
     "ionode_compose_plan", "ionode_compose_order", "ionode_compose_order_host", "ionode_dopri5_composed", "ionode_compose_tail_plan",
+    "ionode_dopri5_objective",
 )
+
+# the kind of the fused objective (include/ionode.h IONODE_OBJECTIVE_*): what a residual adds to its trajectory's sum
+OBJECTIVE_SSE, OBJECTIVE_SAE = 0, 1
+OBJECTIVE_KINDS = {"sse": OBJECTIVE_SSE, "sae": OBJECTIVE_SAE}
 
 # the backward sweep's entry points: their buffers in ABI order -- between (d, it_begin, it_end, n_iter) and stream (include/ionode.h;
 # tests/test_grad_entry_checks.py compares the names with the header's).  argtypes are generated from it, sweep_launch() calls by it.
@@ -130,6 +135,8 @@ def lib():
         L.ionode_compose_order.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.ionode_dopri5_composed.restype = C.c_int
         L.ionode_dopri5_composed.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 13 + [C.c_int64, C.c_int32]
+        L.ionode_dopri5_objective.restype = C.c_int
+        L.ionode_dopri5_objective.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 13 + [C.c_int64, C.c_int32, C.c_int32]
         L.ionode_compose_tail_plan.restype = C.c_int
         L.ionode_compose_tail_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.POINTER(C.c_int64 * 2)]
         L.ionode_compose_order_host.restype = C.c_int
@@ -309,6 +316,14 @@ def _dev_ptr(t, dtype, name, shape=None):
     return C.c_void_p(t.data_ptr())
 
 
+def objective_kind(objective):
+    """"sse" | "sae" -> IONODE_OBJECTIVE_SSE | IONODE_OBJECTIVE_SAE; anything else raises IonodeError."""
+    kind = OBJECTIVE_KINDS.get(objective) if isinstance(objective, str) else None
+    if kind is None:
+        raise IonodeError(f"objective: 'sse' (sum of squared residuals) or 'sae' (sum of absolute residuals), got {objective!r}")
+    return kind
+
+
 _order_cache = {}
 
 
@@ -340,7 +355,7 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
            prot_t0=0.0, prot_dt=1.0, prot_of_traj=None, rtol=1e-7, atol=1e-9, v_oob=-80.0, max_steps=0,
            max_total_steps=0, max_step=0.0, ckpt=None, current=False, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False, tile_waves=0, stats=True,
            step_log=None, t_eval_hint="auto", t_eval_exact=None, sse_ref=None, states=True, out=None, stream=None,
-           v_at_outputs="auto", traj_per_image=0, launch_order="auto", workspace=None, cost_hint="auto"):
+           v_at_outputs="auto", traj_per_image=0, launch_order="auto", workspace=None, cost_hint="auto", objective="sse"):
     """Launch one batched solve.  Every tensor lives on the current HIP device.
 
     launch_order: None (index order), an int32 device permutation [B] (ionode_desc.launch_order: slot s integrates trajectory
@@ -363,7 +378,14 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
     params [B, n_params] f64, prot_v [P, Np] f64, y0 [B, D] f32|f64 (selects the state dtype),
     t_eval [Nt] f64.  Returns dict(y [B, Nt, D], i [B, Nt] | None, status [B] i32, stats [B, 4] i64 | None);
     asynchronous on the current stream.
+
+    objective: the kind of the fused objective that sse_ref asks for.  "sse" (default): sum_k (i_k - ref_k)^2 per trajectory under
+    "sse".  "sae": sum_k |i_k - ref_k| under "sae" ("sse" is then None) -- Nt times the reference's prediction loss
+    torch.mean(torch.abs(pred_yo - data)); same kernels, same summation order, inf for a failed trajectory; forward only.
     """
+    kind = objective_kind(objective)
+    if kind == OBJECTIVE_SAE and sse_ref is None:
+        raise IonodeError("objective='sae' needs sse_ref (the reference currents [P, Nt])")
     if not torch.cuda.is_available():
         raise IonodeError("no HIP device visible: ionode has no CPU fallback")
     B, D = y0.shape
@@ -423,7 +445,7 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
     sse = None
     if sse_ref is not None:  # fused objective: [P, Nt] reference currents -> per-trajectory sum of squared residuals
         _dev_ptr(sse_ref, torch.float64, "sse_ref", (P, Nt))
-        sse = out.get("sse")
+        sse = out.get(objective)
         if sse is None:
             sse = torch.empty((B,), dtype=torch.float64, device=dev)
         desc.sse_ref, desc.sse_out = sse_ref.data_ptr(), sse.data_ptr()
@@ -489,7 +511,7 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
                 if workspace.numel() < plan["workspace_bytes"]:
                     raise IonodeError(f"workspace: {workspace.numel()} bytes, the plan asks for {plan['workspace_bytes']}")
             ws = workspace if workspace is not None else torch.empty((plan["workspace_bytes"],), dtype=torch.uint8, device=dev)
-    rc = lib().ionode_dopri5_composed(
+    rc = lib().ionode_dopri5_objective(   # kind 0 is ionode_dopri5_composed by definition: one call site
         C.byref(desc),
         _dev_ptr(mlp_packed, torch.float32, "mlp_packed"),
         _dev_ptr(params, torch.float64, "params", (B, params.shape[1])),
@@ -506,10 +528,12 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
         C.c_void_p(ws.data_ptr()) if ws is not None else None,
         ws.numel() if ws is not None else 0,
         COST_SOURCE[composed],
+        kind,
     )
     if rc != 0:
         raise IonodeError(f"ionode_dopri5 failed ({rc}): {last_error()}")
-    return {"y": y, "i": i_out, "status": status, "stats": st, "sse": sse, "desc": desc, "v_at_outputs": vtab,
+    return {"y": y, "i": i_out, "status": status, "stats": st, "sse": sse if kind == OBJECTIVE_SSE else None,
+            "sae": sse if kind == OBJECTIVE_SAE else None, "desc": desc, "v_at_outputs": vtab,
             "launch_order": launch_order, "composed": composed, "kernel": lib().ionode_last_kernel_name().decode()}
 
 

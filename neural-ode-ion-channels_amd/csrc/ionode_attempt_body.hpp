@@ -302,7 +302,7 @@
                 else protocol_v(a, pv_[k], tk, vk);
                 const double ik = obs_current<S, D>(a, out, vk);
                 if (io) io[idx] = ik;
-                if (refb) { const double rr = ik - refb[idx]; sacc += rr * rr; }
+                if (refb) { const double rr = ik - refb[idx]; sacc += residual_term(rr, F::objective_kinds ? a.obj_abs : 0); }
               }
             }
           }
@@ -420,11 +420,12 @@
                     else protocol_v(a, a.prot_v + (size_t)owp[jj] * a.Np, tk[u], vk);
                     const double ik = obs_current<S, D>(a, out, vk);
                     if (a.i_out) a.i_out[(size_t)tr * Nt + idx] = ik;
-                    if (a.sse_out) { const double rr = ik - (VTAB ? cur.rf[u] : a.sse_ref[(size_t)owp[jj] * Nt + idx]); rr2[u] = rr * rr; }
+                    if (a.sse_out) { const double rr = ik - (VTAB ? cur.rf[u] : a.sse_ref[(size_t)owp[jj] * Nt + idx]); rr2[u] = rr; }
                   }
                 }
               }
               if (WI && a.sse_out) {
+                residual_terms(rr2, F::objective_kinds ? a.obj_abs : 0);   // the residuals' terms (rr2[u] held the residual itself up to here; 0 for no sample)
                 // the chunk's sum in the canonical tree ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)) over its 8 consecutive samples
                 double g8;
                 if constexpr (PKL == 4) {
@@ -508,7 +509,7 @@
               else protocol_v(a, pvb, tk, vk);
               const double ik = obs_current<S, D>(a, out, vk);
               if (io) io[idx] = ik;
-              if (refb) { const double rr = ik - ((VTAB && c0 == 0) ? rf_first : refb[idx]); sacc += rr * rr; }
+              if (refb) { const double rr = ik - ((VTAB && c0 == 0) ? rf_first : refb[idx]); sacc += residual_term(rr, F::objective_kinds ? a.obj_abs : 0); }
             }
           }
         }

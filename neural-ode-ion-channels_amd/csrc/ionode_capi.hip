@@ -99,6 +99,7 @@ struct Ask {
   bool want_current;    // a current trace or the fused objective
   bool explicit_grid;   // prot_t given
   bool has_step_log;
+  bool abs_objective;   // the fused objective sums absolute residuals (ionode_dopri5_objective)
 };
 
 // The specialised variants are compiled under a CONTRACT (ionode_form.hpp Lean): uniform protocol grid, no step log, no checkpoints --
@@ -161,9 +162,11 @@ int plan_mlp(const ionode_desc *d, Plan *pl, const Ask &k) {
   // tuned tiles with a hidden layer and the run-time-width tile: verified uniform output grid
   const bool lean_tile = L >= 1 && no_side_outputs(d, k) && has_exact_grid(d);
   const bool lean_t64 = t64 && has_exact_grid(d) && !k.want_current && no_side_outputs(d, k);
-  const bool lean_tuned = !t64 && (NT == 13 || NT == 7 || NT == 32) && lean_tile;
   const Net net = vnet ? Net::Lane : t1 ? (t1deep ? Net::Row1Deep : Net::Row1) : t4 ? Net::Tile4 : Net::Tile;
   const int tpt = t64 ? 64 : t32 ? 32 : t1 ? 1 : t4 ? 4 : 16;
+  // (the lean N = 200 16-tile knows the squares alone, KernelForm::objective_kinds: absolute residuals take its general variant)
+  const bool squares_only = net == Net::Tile && NT == 13 && tpt == 16;
+  const bool lean_tuned = !t64 && (NT == 13 || NT == 7 || NT == 32) && lean_tile && !(k.abs_objective && squares_only);
   // ---- 2. the variant ----
   const int G = t64 ? 1 : ((tw == 8 || tw == 2 || tw == 16) ? 4 : tw);
   pl->v = find_variant(d->model, f32, net, lean_t64 ? Lean::States : (lean_tuned ? Lean::Tile : Lean::General), tpt, G, NT);
@@ -293,7 +296,7 @@ bool plan_compose(const ionode_desc *d, const Plan &pl) {
          d->launch_order == nullptr && d->n_traj <= ionode::kComposeMaxB && (int64_t)pl.grid <= (int64_t)compute_units_now();
 }
 
-int make_plan(const ionode_desc *d, Plan *pl, bool want_current = false, bool explicit_grid = false) {
+int make_plan(const ionode_desc *d, Plan *pl, bool want_current = false, bool explicit_grid = false, bool abs_objective = false) {
   if (!d) { set_err("null descriptor"); return IONODE_ERR_ARG; }
 #ifdef IONODE_STAMPS
   const bool has_step_log = false;   // diagnostic build: the step log carries the phase stamps and does not exclude the lean variants
@@ -307,7 +310,7 @@ int make_plan(const ionode_desc *d, Plan *pl, bool want_current = false, bool ex
   if (d->n_traj < 1 || d->n_out < 1 || d->n_prot < 1 || d->prot_n < 2) { set_err("empty batch / grid / protocol"); return IONODE_ERR_ARG; }
   if (d->n_params < (D == 6 ? 12 : 8)) { set_err("n_params too small for model"); return IONODE_ERR_ARG; }
   if (!(d->rtol > 0) || !(d->atol >= 0) || !(d->prot_dt > 0)) { set_err("rtol/atol/prot_dt must be positive"); return IONODE_ERR_ARG; }
-  const Ask k = {want_current, explicit_grid, has_step_log};
+  const Ask k = {want_current, explicit_grid, has_step_log, abs_objective};
   return mlp ? plan_mlp(d, pl, k) : plan_closed(d, pl, k, D);
 }
 
@@ -674,9 +677,9 @@ namespace {
 int dopri5_impl(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
                 const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
                 void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace, int64_t workspace_bytes,
-                int cost_source = 0) {
+                int cost_source = 0, int objective = IONODE_OBJECTIVE_SSE) {
   Plan pl;
-  const int rc = make_plan(d, &pl, i_out != nullptr || d->sse_out != nullptr, prot_t != nullptr);
+  const int rc = make_plan(d, &pl, i_out != nullptr || d->sse_out != nullptr, prot_t != nullptr, objective == IONODE_OBJECTIVE_SAE);
   if (rc != IONODE_OK) return rc;
   const bool mlp = d->model == IONODE_MODEL_NNF || d->model == IONODE_MODEL_NND;
   if (!params || !prot_v || !y0 || !t_eval || (!y_out && !d->sse_out) || !status || (mlp && !mlp_packed)) {
@@ -704,6 +707,7 @@ int dopri5_impl(const ionode_desc *d, const float *mlp_packed, const double *par
   a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only;
   a.step_log = d->step_log; a.step_log_cap = d->step_log ? d->step_log_cap : 0;
   a.sse_ref = d->sse_ref; a.sse_out = d->sse_out; a.v_tab = d->v_at_outputs;
+  a.obj_abs = objective == IONODE_OBJECTIVE_SAE ? 1 : 0;
   if (mlp && d->traj_per_image > 0) { a.mlp_stride = d->mlp_image_stride; a.traj_per_img = d->traj_per_image; }  // checked in make_plan
   if (d->launch_order) {
     if (a.traj_per_img > 0) { set_err("launch_order cannot be combined with traj_per_image (tiles of an image must stay together)"); return IONODE_ERR_ARG; }
@@ -774,6 +778,28 @@ int ionode_dopri5_composed(const ionode_desc *d, const float *mlp_packed, const 
   if (cost_source < 0 || cost_source > 2) { set_err("cost_source: 0 (not composed), 1 (pilot) or 2 (counts)"); return IONODE_ERR_ARG; }
   return dopri5_impl(d, mlp_packed, params, prot_v, prot_t, prot_of_traj, y0, t_eval, y_out, i_out, status, stats, stream, workspace,
                      workspace_bytes, cost_source);
+}
+
+int ionode_dopri5_objective(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
+                            const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,
+                            void *y_out, double *i_out, int32_t *status, int64_t *stats, void *stream, void *workspace,
+                            int64_t workspace_bytes, int32_t cost_source, int32_t objective) {
+  // the kind first: whatever else is wrong with the call, an unknown kind or absolute values without a fused objective is what it reports
+  if (objective != IONODE_OBJECTIVE_SSE && objective != IONODE_OBJECTIVE_SAE) {
+    set_err("ionode_dopri5_objective: objective must be IONODE_OBJECTIVE_SSE (0) or IONODE_OBJECTIVE_SAE (1)");
+    return IONODE_ERR_ARG;
+  }
+  if (objective == IONODE_OBJECTIVE_SAE && (d == nullptr || d->sse_out == nullptr)) {
+    set_err("ionode_dopri5_objective: IONODE_OBJECTIVE_SAE needs the fused objective's output, d->sse_out");
+    return IONODE_ERR_ARG;
+  }
+  if (objective == IONODE_OBJECTIVE_SSE) {
+    return ionode_dopri5_composed(d, mlp_packed, params, prot_v, prot_t, prot_of_traj, y0, t_eval, y_out, i_out, status, stats, stream,
+                                  workspace, workspace_bytes, cost_source);
+  }
+  if (cost_source < 0 || cost_source > 2) { set_err("cost_source: 0 (not composed), 1 (pilot) or 2 (counts)"); return IONODE_ERR_ARG; }
+  return dopri5_impl(d, mlp_packed, params, prot_v, prot_t, prot_of_traj, y0, t_eval, y_out, i_out, status, stats, stream, workspace,
+                     workspace_bytes, cost_source, objective);
 }
 
 int ionode_protocol_at_outputs(const ionode_desc *d, const double *prot_v, const double *prot_t, const double *t_eval,

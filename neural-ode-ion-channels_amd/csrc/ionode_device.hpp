@@ -277,7 +277,7 @@ __global__ void __launch_bounds__((KernelForm<MODEL, G, RT, NT, PD, TAIL>::block
     double v0;
     protocol_v(a, pv, t, v0);
     const double r0 = obs_current<S, D>(a, y, v0) - a.sse_ref[(size_t)pidx * Nt];
-    sse = r0 * r0;
+    sse = residual_term(r0, F::objective_kinds ? a.obj_abs : 0);
   }
 
   int oi = 1;  // next output index

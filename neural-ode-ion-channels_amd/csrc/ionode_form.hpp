@@ -82,6 +82,10 @@ template <int MODEL, int G, int RT, int NT, int PD, int TAIL> struct KernelForm 
   // ... and, given a record workspace, leaves the dense output of its accepted steps to ionode_dense_expand_kernel: a step writes one
   // record (ionode_dense_expand.hpp DenseRecord) instead of evaluating and storing its samples between two evaluations of the net
   static constexpr bool defer = shrink;
+  // ... and knows the fused objective's squares alone (KArgs::obj_abs is not read): these four kernels fill the register file -- NN-d
+  // fp64 all 512 registers without a spill -- and a flag in their emission, in whatever form, made that one spill 4 to 8 vector
+  // registers.  The host sends a sum of absolute residuals on the 16-tile to the general variant (ionode_capi.hip plan_mlp).
+  static constexpr bool objective_kinds = !shrink;
 
   using Tile = MlpTile<G, (t64 ? 1 : (RT > 0 ? RT : 1)), (NT > 0 ? NT : 1), ((PD > 0 && net != Net::Lane) ? PD : 1), nsets>;
   using Mlp = std::conditional_t<net == Net::None, NoMlp,

@@ -106,6 +106,31 @@ template <typename S, int D, typename A> __device__ __forceinline__ double obs_c
   return (double)gate * (v - a.obs_e);
 }
 
+// ---- the fused objective's residual term ----
+// What one sample's residual rr = i_k - ref_k adds to its trajectory's sum: rr^2 (obj_abs == 0, the sum of squares) or |rr| (1, the
+// reference's prediction loss torch.mean(torch.abs(pred_yo - data)) times the sample count).  obj_abs is wave-uniform (KArgs), read at
+// run time: the summation trees around the term are the same for both kinds, and a kind per instantiation would double the kernels.
+// A wave-uniform BRANCH, which the empty asm keeps hipcc from turning into a select: as a select (an and, two v_cndmask per sample)
+// the squares of the 6-state table kernel, which runs one wavefront per SIMD and pays for every instruction, came out 2.8 % slower
+// (profiles/objective_kinds.md).  Kernels whose KernelForm::objective_kinds is false pass 0 and keep the multiply alone.
+__device__ __forceinline__ double residual_term(double rr, int obj_abs) {
+  if (__builtin_expect(obj_abs != 0, 0)) {
+    asm volatile("");
+    return fabs(rr);
+  }
+  return rr * rr;
+}
+// ... of the N residuals a lane holds for one chunk of the work-list emission, in place: one branch for the N of them.
+template <int N> __device__ __forceinline__ void residual_terms(double (&rr)[N], int obj_abs) {
+  if (__builtin_expect(obj_abs != 0, 0)) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) rr[u] = residual_term(rr[u], 1);
+  } else {
+#pragma unroll
+    for (int u = 0; u < N; ++u) rr[u] = residual_term(rr[u], 0);
+  }
+}
+
 // ---- one step's interpolant, wave-uniform, as an emission loop holds it ----
 template <typename S, int D> struct Interp {
   using R = InterpRow<D>;

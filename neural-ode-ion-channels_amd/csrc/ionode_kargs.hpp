@@ -32,6 +32,8 @@ struct KArgs {
   double prot_rdt;     // 1.0 / prot_dt, correctly rounded (host division): divisions by prot_dt become div_by()
   double dt_max;       // optional cap on the step size (+inf: none -- torchdiffeq 0.2.1 has no such option)
   int32_t obs_open;
+  int32_t obj_abs;     // fused objective, the term a residual adds (ionode_interp.hpp residual_term): 0 = its square, 1 = its absolute value;
+                       // wave-uniform.  It sits in what was padding, so every other field keeps its offset
   double *step_log;
   int64_t step_log_cap;
   const double *sse_ref;  // fused objective (hint path): reference currents [P][Nt]; per trajectory sum_k (i_k - ref[prot][k])^2 ...

@@ -87,3 +87,23 @@ def sharded_mean_abs_loss(solve_shard, i_ref, n_traj, group=None):
     ref = torch.as_tensor(ref, dtype=pred.dtype, device=pred.device)
     s, c = allreduce_sum_count((pred - ref).abs().sum(), pred.numel(), group=group)
     return s / c
+
+
+def sharded_mean_abs_loss_fused(solve_shard, n_traj, n_out, group=None):
+    """sharded_mean_abs_loss without the traces: the global mean |i_pred - i_ref| over `n_traj` trajectories of `n_out` samples each.
+
+    solve_shard(lo, hi) -> [hi - lo] fused sums of absolute residuals of this rank's trajectories (Solution.sae of a solve with
+    sse_ref and objective="sae": the reference currents never leave the kernel's side).  One allreduce_sum_count of
+    (sum, (hi - lo) * n_out) follows.  A failed trajectory's inf makes the mean inf.
+    """
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+    else:
+        rank, world = 0, 1
+    lo, hi = shard_bounds(n_traj, rank, world)
+    sae = solve_shard(lo, hi)
+    if tuple(sae.shape) != (hi - lo,):
+        raise ValueError(f"solve_shard({lo}, {hi}) returned shape {tuple(sae.shape)}, expected {(hi - lo,)}")
+    s, c = allreduce_sum_count(sae.sum(), (hi - lo) * n_out, group=group)
+    return s / c

@@ -35,6 +35,38 @@ def population_sum_of_squares(candidates, protocols_v, data_i, t_eval, *, base_p
     `solver` (tests only): a stand-in with batched.solve's signature, so the sharding / all-gather logic can run under
     gloo on a box without a GPU; the product default is the HIP solve and there is no CPU fallback.
     """
+    return _population_error("sse", False, candidates, protocols_v, data_i, t_eval, base_params=base_params, free=free, prot_t0=prot_t0,
+                             prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e, max_total_steps=max_total_steps,
+                             group=group, device=device, solver=solver, fused=fused, cost=cost, model=model, weights=weights,
+                             mlp_layers=mlp_layers, mlp_width=mlp_width, weights_key=weights_key)
+
+
+def population_mean_abs_error(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), prot_t0=0.0,
+                              prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
+                              max_total_steps=1_000_000, group=None, device=None, solver=None, fused=True, cost=None,
+                              model=capi.MODEL_HH2, weights=None, mlp_layers=0, mlp_width=0, weights_key=None, per_protocol=False):
+    """Mean absolute error of every candidate: the reference's prediction loss torch.mean(torch.abs(pred_yo - data)) (every --pred
+    section, train-s1.py:275-353; the validation that picks the best checkpoint, train-r1.py:930-959), for a whole population.
+
+    The sibling of population_sum_of_squares: same arguments, sharding, padding for weights [C, n], all-gather and `solver`
+    stand-in.  Returns a [C] fp64 tensor on the device, the mean of |i - data| over the candidate's P * Nt samples; inf where any
+    of the candidate's solves failed.  per_protocol=True: [C, P], the mean over each protocol's Nt samples (the reference sums
+    per-protocol means when it ranks checkpoints, train-r1.py:953); a candidate with a failed solve is inf in every column.
+    fused (default): the absolute residuals are accumulated inside the kernel (capi.dopri5(objective="sae")) and no trace is
+    written; fused=False stores the current traces and reduces them with torch (for tests).  A `solver` stand-in serves either
+    route: its Solution carries .sae [B] for the fused one, .i [B, Nt] for the other.
+    """
+    return _population_error("sae", per_protocol, candidates, protocols_v, data_i, t_eval, base_params=base_params, free=free,
+                             prot_t0=prot_t0, prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e,
+                             max_total_steps=max_total_steps, group=group, device=device, solver=solver, fused=fused, cost=cost,
+                             model=model, weights=weights, mlp_layers=mlp_layers, mlp_width=mlp_width, weights_key=weights_key)
+
+
+def _population_error(kind, per_protocol, candidates, protocols_v, data_i, t_eval, *, base_params, free, prot_t0, prot_dt, y0,
+                      state_dtype, obs_g, obs_e, max_total_steps, group, device, solver, fused, cost, model, weights, mlp_layers,
+                      mlp_width, weights_key):
+    """The one body of population_sum_of_squares (kind "sse": [C] sums) and population_mean_abs_error (kind "sae": [C] means, or
+    [C, P] per-protocol means): shard the candidates, solve, reduce each candidate's P sweeps, all-gather."""
     import torch.distributed as dist
     cand = np.asarray(candidates, dtype=np.float64)
     C, P = cand.shape[0], np.asarray(protocols_v).shape[0]
@@ -58,31 +90,40 @@ def population_sum_of_squares(candidates, protocols_v, data_i, t_eval, *, base_p
             raise capi.IonodeError("weights [C, n]: one weight set per candidate")
         S = 16 * ((P + 15) // 16)
         mlp.update(weights=np.asarray(weights)[lo:hi], traj_per_image=S, weights_key=None)
-    sse = torch.full((hi - lo,), float("inf"), dtype=torch.float64, device=dev)
+    cols = (P,) if per_protocol else ()
+    out = torch.full((hi - lo,) + cols, float("inf"), dtype=torch.float64, device=dev)
     if hi > lo:
         params = np.tile(np.asarray(base_params, dtype=np.float64), (hi - lo, 1))
         params[:, list(free)] = cand[lo:hi]
         params = np.repeat(params, S, axis=0)                       # candidate-major: trajectory = c*S + p
         pot = np.tile(np.where(np.arange(S) < P, np.arange(S), 0).astype(np.int32), hi - lo)
         ref = torch.as_tensor(np.asarray(data_i), dtype=torch.float64, device=dev)     # [P, Nt]
-        if fused and solver is None:
+        # (the squares' stand-ins return traces only, so a stand-in takes the fused route for the absolute values alone)
+        if fused and (solver is None or kind == "sae"):
             sol = solve(model, params, protocols_v, torch.tensor([list(y0)], dtype=state_dtype), t_eval,
                         prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=pot, obs_g=obs_g, obs_e=obs_e,
-                        max_total_steps=max_total_steps, device=dev, sse_ref=ref.contiguous(), states=False, **mlp)
-            err = sol.sse.reshape(hi - lo, S)[:, :P].sum(dim=1)      # failed solves are inf already
+                        max_total_steps=max_total_steps, device=dev, sse_ref=ref.contiguous(), states=False,
+                        **({} if kind == "sse" else {"objective": kind}), **mlp)
+            per = getattr(sol, kind).reshape(hi - lo, S)[:, :P]     # failed solves are inf already
         else:
             sol = solve(model, params, protocols_v, torch.tensor([list(y0)], dtype=state_dtype), t_eval,
                         prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=pot, current=True, obs_g=obs_g, obs_e=obs_e,
                         max_total_steps=max_total_steps, device=dev, **mlp)
-            err = ((sol.i.reshape(hi - lo, S, -1)[:, :P] - ref[None]) ** 2).sum(dim=(1, 2))
+            res = sol.i.reshape(hi - lo, S, -1)[:, :P] - ref[None]
+            per = None if kind == "sse" else res.abs().sum(dim=2)
+        if kind == "sse":
+            err = per.sum(dim=1) if per is not None else (res ** 2).sum(dim=(1, 2))
+        else:
+            Nt = ref.shape[1]
+            err = per / Nt if per_protocol else per.sum(dim=1) / (P * Nt)
         ok = (sol.status.reshape(hi - lo, S)[:, :P] == 0).all(dim=1)
-        sse = torch.where(ok, err, torch.full_like(err, float("inf")))
+        out = torch.where(ok[:, None] if per_protocol else ok, err, torch.full_like(err, float("inf")))
     if world == 1:
-        return sse
+        return out
     # all-gather of unequal shards: pad to the largest shard
     m = max(b[1] - b[0] for b in bounds)
-    pad = torch.full((m,), float("inf"), dtype=torch.float64, device=dev)
-    pad[: hi - lo] = sse
+    pad = torch.full((m,) + cols, float("inf"), dtype=torch.float64, device=dev)
+    pad[: hi - lo] = out
     parts = [torch.empty_like(pad) for _ in range(world)]
     dist.all_gather(parts, pad, group=group)
     return torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
