@@ -241,7 +241,7 @@ int ionode_compose_order_host(const double *cost, int32_t n_traj, int32_t *order
  *   IONODE_OBJECTIVE_SSE  sum_k (i_k - sse_ref[protocol][k])^2 -- what sse_out has always held (PINTS SumOfSquaresError);
  *   IONODE_OBJECTIVE_SAE  sum_k |i_k - sse_ref[protocol][k]| -- n_out times the reference's prediction loss
  *                         torch.mean(torch.abs(pred_yo - data)) (train-s1.py:275-353, the validation of train-r1.py:930-959), which it
- *                         only ever evaluates under torch.no_grad(): a forward quantity, the backward entry points do not know it.
+ *                         only ever evaluates under torch.no_grad(); its gradient: ionode_objective_backward[_gc]() below.
  * Same kernels, same summation order, same inf for a failed trajectory: the kind is a wave-uniform kernel argument that selects the
  * term a residual contributes (csrc/ionode_interp.hpp residual_term), and with IONODE_OBJECTIVE_SSE every output is bit for bit what
  * the earlier entry points write.  One exception in the choice of kernel, none in the results: the lean N = 200 16-trajectory tile
@@ -394,6 +394,31 @@ int ionode_dopri5_backward_sweep_sse(const ionode_desc *d, int32_t it_begin, int
                                      const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
                                      const double *t_eval, const int32_t *n_accepted, const double *sse_grad_y0, double *state,
                                      float *records, const double *packets, double *grad_params, double *grad_y0, void *stream);
+
+/*
+ * The gradient of the fused objective of either kind (IONODE_OBJECTIVE_*; since ABI 10, added later: new symbols only, ionode_desc and
+ * every earlier entry point unchanged).  The forward is ionode_dopri5_objective() with the same `objective`, d->ckpt and d->sse_out
+ * set; grad_sse[b] = dL/dsse_out[b] is the upstream gradient of that trajectory's sum, whatever its kind.  A sample's residual
+ * r_k = i_k - sse_ref[protocol][k] enters the sweep through one weight w_k = d term / d r_k times grad_sse[b]
+ * (csrc/ionode_interp.hpp residual_weight), dL/dy_k = w_k dr_k/dy_k:
+ *   IONODE_OBJECTIVE_SSE  w_k = 2 grad_sse[b] r_k
+ *   IONODE_OBJECTIVE_SAE  w_k = grad_sse[b] sign(r_k), sign(0) = 0 and sign(NaN) = NaN: the subgradient torch.abs's backward takes,
+ *                         so that this is the derivative of n_out times the reference's torch.mean(torch.abs(pred_yo - data))
+ * Only the two launches that form the weights know the kind:
+ *   ionode_objective_backward()     ionode_dopri5_backward_sse() (closed-form models) plus `objective`;
+ *   ionode_objective_backward_gc()  ionode_dopri5_backward_sse_gc() (NN-f / NN-d) plus `objective`; the rest of a chunk is
+ *                                   ionode_dopri5_backward_recompute_sse(), ionode_dopri5_backward_sweep_sse() and
+ *                                   ionode_grad_reduce_unit() for both kinds: the products and the walk never see a residual.
+ * With IONODE_OBJECTIVE_SSE both are those entry points bit for bit.  IONODE_ERR_ARG, checked before any other argument and before
+ * any launch, for another value of `objective`; every other refusal is the squares' entry point's, code and text.
+ */
+int ionode_objective_backward(const ionode_desc *d, int32_t objective, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *params,
+                              const double *prot_v, const double *prot_t, const int32_t *prot_of_traj, const double *t_eval,
+                              const int32_t *n_accepted, const double *grad_sse, double *state, double *grad_params,
+                              double *grad_y0, void *stream);
+int ionode_objective_backward_gc(const ionode_desc *d, int32_t objective, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *prot_v,
+                                 const double *prot_t, const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
+                                 const double *grad_sse, double *packets, double *sse_grad_y0, void *stream);
 
 /* floats of one slab's partial gradient: [NP][4]{db0, dW0[.][0], dW0[.][1], 0} | L x (dW_l [NP][NP] + db_l [NP]) | dwl [NP] +
  * {dbl, 0, 0, 0}, NP = 16 * ceil(N / 16), rows/columns >= N are padding */

@@ -33,7 +33,7 @@ EXPORTS = (
     "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh", "ionode_regress_plan",
     "ionode_dense_defer_plan", "ionode_dense_tail_plan", "ionode_dopri5_deferred",
     "ionode_compose_plan", "ionode_compose_order", "ionode_compose_order_host", "ionode_dopri5_composed", "ionode_compose_tail_plan",
-    "ionode_dopri5_objective",
+    "ionode_dopri5_objective", "ionode_objective_backward", "ionode_objective_backward_gc",
 )
 
 # the kind of the fused objective (include/ionode.h IONODE_OBJECTIVE_*): what a residual adds to its trajectory's sum
@@ -56,6 +56,14 @@ SWEEP_BUFFERS = {
                                              "packets"),
     "ionode_dopri5_backward_sweep_sse": ("grad_image", "params", "prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "sse_grad_y0",
                                          "state", "records", "packets", "grad_params", "grad_y0"),
+}
+
+# the fused objective's gradient of either kind (include/ionode.h): the two launches that form the residuals' weights.  Their buffers
+# in ABI order -- between (d, objective, it_begin, it_end, n_iter) and stream: those of the squares' entry points, which they are with
+# OBJECTIVE_SSE.  objective_launch() calls by these names.
+OBJECTIVE_BUFFERS = {
+    "ionode_objective_backward": SWEEP_BUFFERS["ionode_dopri5_backward_sse"],
+    "ionode_objective_backward_gc": SWEEP_BUFFERS["ionode_dopri5_backward_sse_gc"],
 }
 
 
@@ -152,6 +160,9 @@ def lib():
         for name, buffers in SWEEP_BUFFERS.items():
             getattr(L, name).restype = C.c_int
             getattr(L, name).argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * (len(buffers) + 1)
+        for name, buffers in OBJECTIVE_BUFFERS.items():
+            getattr(L, name).restype = C.c_int
+            getattr(L, name).argtypes = [C.POINTER(IonodeDesc)] + [C.c_int32] * 4 + [C.c_void_p] * (len(buffers) + 1)
         L.ionode_grad_reduce.restype = C.c_int
         L.ionode_grad_reduce.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
         L.ionode_grad_reduce_slabs.restype = C.c_int32
@@ -381,7 +392,8 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
 
     objective: the kind of the fused objective that sse_ref asks for.  "sse" (default): sum_k (i_k - ref_k)^2 per trajectory under
     "sse".  "sae": sum_k |i_k - ref_k| under "sae" ("sse" is then None) -- Nt times the reference's prediction loss
-    torch.mean(torch.abs(pred_yo - data)); same kernels, same summation order, inf for a failed trajectory; forward only.
+    torch.mean(torch.abs(pred_yo - data)); same kernels, same summation order, inf for a failed trajectory.  With its gradient:
+    grad.sum_of_abs.
     """
     kind = objective_kind(objective)
     if kind == OBJECTIVE_SAE and sse_ref is None:
@@ -559,6 +571,18 @@ def sweep_launch(name, desc, it_begin, it_end, n_iter, stream, **buffers):
         raise TypeError(f"{name}: missing {sorted(set(names) - set(buffers))}, unknown {sorted(set(buffers) - set(names))}")
     ptrs = [None if buffers[n] is None else C.c_void_p(buffers[n].data_ptr()) for n in names]
     rc = getattr(lib(), name)(C.byref(desc), it_begin, it_end, n_iter, *ptrs, C.c_void_p(stream.cuda_stream))
+    if rc != 0:
+        raise IonodeError(f"{name} failed ({rc}): {lib().ionode_grad_last_error().decode()}")
+
+
+def objective_launch(name, desc, kind, it_begin, it_end, n_iter, stream, **buffers):
+    """sweep_launch for the entry points of OBJECTIVE_BUFFERS, which take the objective's kind (OBJECTIVE_SSE | OBJECTIVE_SAE) behind
+    the descriptor: the same named-buffer call, the same error."""
+    names = OBJECTIVE_BUFFERS[name]
+    if set(buffers) != set(names):
+        raise TypeError(f"{name}: missing {sorted(set(names) - set(buffers))}, unknown {sorted(set(buffers) - set(names))}")
+    ptrs = [None if buffers[n] is None else C.c_void_p(buffers[n].data_ptr()) for n in names]
+    rc = getattr(lib(), name)(C.byref(desc), int(kind), it_begin, it_end, n_iter, *ptrs, C.c_void_p(stream.cuda_stream))
     if rc != 0:
         raise IonodeError(f"{name} failed ({rc}): {lib().ionode_grad_last_error().decode()}")
 

@@ -516,13 +516,14 @@ __device__ __forceinline__ void sse_fit_step(double dt, const double (&y)[D], co
 }
 
 // One output sample of the step: y_k from the interpolant at x (state dtype: interp_eval), its residual against `ref` at voltage
-// v, and P[c][d] += g2 r_k dr_k/dy_d x^c in fp64 (g2 = 2 dL/dsse[b]).
-template <typename S, int D>
-__device__ __forceinline__ void sse_sample_term(const GArgs &a, const S (&cf)[5][D], S xs, double v, double ref, double g2, double (&P)[5][D]) {
+// v, and P[c][d] += w_k dr_k/dy_d x^c in fp64, w_k = residual_weight(r_k, g, ABS) with g = dL/dsum[b]: 2 g r_k for the squares,
+// g sign(r_k) for the absolute values.  ABS is a constant: the callers branch on KArgs::obj_abs around their sample loops.
+template <typename S, int D, int ABS>
+__device__ __forceinline__ void sse_sample_term(const GArgs &a, const S (&cf)[5][D], S xs, double v, double ref, double g, double (&P)[5][D]) {
   S out[D];
   interp_eval<S, D>(cf, xs, out);
   double dr[D];
-  const double gr = g2 * sse_residual<S, D>(a, out, v, ref, dr);
+  const double gr = residual_weight(sse_residual<S, D>(a, out, v, ref, dr), g, ABS);
   const double x = (double)xs;
   double xp = 1.0;
 #pragma unroll
@@ -531,6 +532,14 @@ __device__ __forceinline__ void sse_sample_term(const GArgs &a, const S (&cf)[5]
     for (int d = 0; d < D; ++d) P[c][d] += (gr * dr[d]) * xp;
     xp *= x;
   }
+}
+
+// The sample loop of one step, once per kind: `samples(kind)` runs it with kind() as sse_sample_term's ABS.  One wave-uniform branch
+// per step and trajectory (the forward's flag cost the 6-state squares 2.8 % as a per-sample select and nothing as a hoisted branch:
+// profiles/objective_kinds.md).
+template <typename F> __device__ __forceinline__ void sse_step_samples(int obj_abs, F &&samples) {
+  if (__builtin_expect(obj_abs != 0, 0)) samples(std::integral_constant<int, 1>{});
+  else samples(std::integral_constant<int, 0>{});
 }
 
 // One-phase backward sweep; SSE: the fused sum-of-squares variant (closed-form models only).  Only the source of the output

@@ -118,7 +118,7 @@ const Entry RECOMPUTE_SSE = {"ionode_dopri5_backward_recompute_sse", Family::NN,
 const Entry SWEEP_SSE = {"ionode_dopri5_backward_sweep_sse", Family::NN, Order::SseNN, Sweep::Walk, true, nullptr, OLDEST_NULL,
                          [](const Buffers &b) { return b.params && b.sse_grad_y0 && adjoint(b); }};
 
-int checked_launch(const Entry &e, const ionode_desc *d, const Buffers &b) {
+int checked_launch(const Entry &e, const ionode_desc *d, const Buffers &b, int obj_abs = 0) {
   constexpr const char *TWO_PHASE = "two-phase sweep: NN-f / NN-d only, `packets` required";
   constexpr const char *VARIANTS = "backward sweep: (L, N) outside the compiled variants (N pads to 16, 112, 208 or 512; at most 15 hidden layers)";
   if (!d) return refuse(IONODE_ERR_ARG, "null descriptor");
@@ -174,6 +174,7 @@ int checked_launch(const Entry &e, const ionode_desc *d, const Buffers &b) {
   if (e.sse_ref) {
     a.grad_sse = b.grad_sse; a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
     a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
+    a.k.obj_abs = obj_abs;   // (the kind of the fused objective: read by the two kernels that form the residuals' weights)
   }
   fn(a, (unsigned)((a.k.B + 15) / 16), lds, reinterpret_cast<hipStream_t>(b.stream));
   const hipError_t err = hipGetLastError();
@@ -314,6 +315,35 @@ int ionode_dopri5_backward_sweep_sse(const ionode_desc *d, int32_t it_begin, int
   b.sse_grad_y0 = const_cast<double *>(sse_grad_y0); b.state = state; b.records = records; b.packets = const_cast<double *>(packets);
   b.grad_params = grad_params; b.grad_y0 = grad_y0; b.stream = stream;
   return checked_launch(SWEEP_SSE, d, b);
+}
+
+// ---- the fused objective of either kind (IONODE_OBJECTIVE_*): the two launches that form the residuals' adjoint weights ----
+// The kind is checked first, as ionode_dopri5_objective checks it; everything else is the squares' entry point's row and checks.
+static int objective_kind(const char *who, int32_t objective) {
+  if (objective == IONODE_OBJECTIVE_SSE || objective == IONODE_OBJECTIVE_SAE) return 0;
+  return refuse(IONODE_ERR_ARG, "%s: objective must be IONODE_OBJECTIVE_SSE (0) or IONODE_OBJECTIVE_SAE (1)", who);
+}
+
+int ionode_objective_backward(const ionode_desc *d, int32_t objective, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *params,
+                              const double *prot_v, const double *prot_t, const int32_t *prot_of_traj, const double *t_eval,
+                              const int32_t *n_accepted, const double *grad_sse, double *state, double *grad_params,
+                              double *grad_y0, void *stream) {
+  if (const int rc = objective_kind("ionode_objective_backward", objective)) return rc;
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.params = params; b.prot_v = prot_v; b.prot_t = prot_t;
+  b.prot_of_traj = prot_of_traj; b.t_eval = t_eval; b.n_accepted = n_accepted; b.grad_sse = grad_sse; b.state = state;
+  b.grad_params = grad_params; b.grad_y0 = grad_y0; b.stream = stream;
+  return checked_launch(BACKWARD_SSE, d, b, objective == IONODE_OBJECTIVE_SAE ? 1 : 0);
+}
+
+int ionode_objective_backward_gc(const ionode_desc *d, int32_t objective, int32_t it_begin, int32_t it_end, int32_t n_iter, const double *prot_v,
+                                 const double *prot_t, const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
+                                 const double *grad_sse, double *packets, double *sse_grad_y0, void *stream) {
+  if (const int rc = objective_kind("ionode_objective_backward_gc", objective)) return rc;
+  Buffers b = {};
+  b.it_begin = it_begin; b.it_end = it_end; b.n_iter = n_iter; b.prot_v = prot_v; b.prot_t = prot_t; b.prot_of_traj = prot_of_traj;
+  b.t_eval = t_eval; b.n_accepted = n_accepted; b.grad_sse = grad_sse; b.packets = packets; b.sse_grad_y0 = sse_grad_y0; b.stream = stream;
+  return checked_launch(SSE_GC, d, b, objective == IONODE_OBJECTIVE_SAE ? 1 : 0);
 }
 
 static int reduce_impl(int32_t L, int32_t N, const float *records, int64_t n_records, int32_t n_slabs, float *partials, void *stream,

@@ -5,7 +5,8 @@
 // sse[b] = sum_k (i_k - ref_k)^2 both depend on the step's checkpoint, the protocol, the reference trace and the upstream scalar
 // dL/dsse[b] -- not on the net and not on the adjoint.  ionode_grad_sse_gc_kernel forms them for every (trajectory, step) of a
 // chunk: the recompute kernel then runs with grad_y == NULL (it leaves the GC slots alone) and the walk takes the sample-0 term
-// from a [B][D] buffer, so no [B][Nt] array exists anywhere on the route.
+// from a [B][D] buffer, so no [B][Nt] array exists anywhere on the route.  The sum of absolute values, sae[b] = sum_k |i_k - ref_k|
+// (GArgs::k.obj_abs = 1, ionode_objective_backward_gc), differs in the samples' weights alone: residual_weight (ionode_interp.hpp).
 //
 // The step's dense-output fit and the per-sample term are sse_fit_step / sse_sample_term (ionode_grad.hpp), which the closed-form
 // one-phase sweep (ionode_grad_sweep_body.hpp, SSE = true) calls too; both stand on the forward's interpolant (ionode_interp.hpp).
@@ -40,7 +41,7 @@ __global__ void __launch_bounds__(64 * GRAD_GC_WAVES) ionode_grad_sse_gc_kernel(
   const double *__restrict__ ref = a.sse_ref + (size_t)pidx * Nt;
   const double *__restrict__ vt = a.v_tab ? a.v_tab + (size_t)pidx * Nt : nullptr;
   const double *__restrict__ ck = a.ckpt + (size_t)b * a.ckpt_cap * RECW;
-  const double g2 = 2.0 * a.grad_sse[b];
+  const double gb = a.grad_sse[b];
 
   double P[5][D];
 #pragma unroll
@@ -62,17 +63,19 @@ __global__ void __launch_bounds__(64 * GRAD_GC_WAVES) ionode_grad_sse_gc_kernel(
       S cf[5][D];
       sse_fit_step<S, D>(rec[CK::DT], ys, ks, (s + 1 < nst && s + 1 < a.ckpt_cap) ? rec + RECW + CK::Y : nullptr, cf);
       const double den = t1 - t0, rden = 1.0 / den;   // the forward's reciprocal and div_pos: the same x bits
-      for (int c0 = 0; c0 < n; c0 += 64) {
-        const int idx = oi + c0 + lane;
-        if (c0 + lane < n && idx >= 0 && idx < Nt) {
-          const double tk = a.k.t_eval[idx];
-          const S xs = interp_x<S>(tk, t0, den, rden);
-          double vk;
-          if (vt) vk = vt[idx];
-          else protocol_v(a.k, pv, tk, vk);
-          sse_sample_term<S, D>(a, cf, xs, vk, ref[idx], g2, P);
+      sse_step_samples(a.k.obj_abs, [&](auto kind) {
+        for (int c0 = 0; c0 < n; c0 += 64) {
+          const int idx = oi + c0 + lane;
+          if (c0 + lane < n && idx >= 0 && idx < Nt) {
+            const double tk = a.k.t_eval[idx];
+            const S xs = interp_x<S>(tk, t0, den, rden);
+            double vk;
+            if (vt) vk = vt[idx];
+            else protocol_v(a.k, pv, tk, vk);
+            sse_sample_term<S, D, decltype(kind)::value>(a, cf, xs, vk, ref[idx], gb, P);
+          }
         }
-      }
+      });
 #pragma unroll
       for (int m = 32; m >= 1; m >>= 1)
 #pragma unroll
@@ -95,7 +98,7 @@ __global__ void __launch_bounds__(64 * GRAD_GC_WAVES) ionode_grad_sse_gc_kernel(
     if (vt) v0 = vt[0];
     else protocol_v(a.k, pv, a.k.t_eval[0], v0);
     double dr[D];
-    const double gr = g2 * sse_residual<S, D>(a, y0s, v0, ref[0], dr);
+    const double gr = residual_weight(sse_residual<S, D>(a, y0s, v0, ref[0], dr), gb, a.k.obj_abs);
 #pragma unroll
     for (int d = 0; d < D; ++d) s0[d] = gr * dr[d];
   }

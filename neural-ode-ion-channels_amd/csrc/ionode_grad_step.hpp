@@ -23,9 +23,10 @@ struct GArgs {
   int64_t record_floats;
   double *packets;            // two-phase sweep: the adjoint-independent scalars of every (tile, step): [n_tiles][it_end - it_begin][16][GRAD_PACKET] fp64
   int32_t reserved;           // (was the host's kernel selector; kept so that the offsets of the fields behind it, and with them every kernel's argument loads, stay as they were)
-  // fused sum-of-squares seed (ionode_dopri5_backward_sse_kernel; grad_y unused): dL/dy_k is formed in the kernel from
-  // dL/dsse[b] and the residual of sample k against sse_ref -- no [B][Nt][D] gradient exists
-  const double *grad_sse;     // [B] upstream dL/dsse
+  // fused objective's seed (ionode_dopri5_backward_sse_kernel; grad_y unused): dL/dy_k is formed in the kernel from
+  // dL/dsse[b] and the residual of sample k against sse_ref -- no [B][Nt][D] gradient exists.  k.obj_abs: the objective's kind
+  // (squares or absolute values: residual_weight, ionode_interp.hpp)
+  const double *grad_sse;     // [B] upstream dL/dsse: the gradient of the trajectory's sum, whichever kind it is
   const double *sse_ref;      // [P][Nt] reference currents
   const double *v_tab;        // optional [P][Nt] V(t_k) (ionode_protocol_at_outputs), or NULL: protocol_v per sample
   double obs_g, obs_e;

@@ -104,18 +104,20 @@
           const double *__restrict__ pvb = a.k.prot_v + (size_t)pj * a.k.Np;
           const double *__restrict__ refb = a.sse_ref + (size_t)pj * Nt;
           const double *__restrict__ vtb = a.v_tab ? a.v_tab + (size_t)pj * Nt : nullptr;
-          const double g2 = 2.0 * a.grad_sse[tr];
+          const double gb = a.grad_sse[tr];
           const double den = t1b - t0b, rden = 1.0 / den;   // the forward's reciprocal and div_pos: the same x bits
-          for (int c0 = 0; c0 < n; c0 += 64) {
-            if (c0 + lane < n) {
-              const int idx = o + c0 + lane;
-              const double tk = a.k.t_eval[idx];
-              double vk;
-              if (vtb) vk = vtb[idx];
-              else protocol_v(a.k, pvb, tk, vk);
-              sse_sample_term<S, D>(a, cb, interp_x<S>(tk, t0b, den, rden), vk, refb[idx], g2, P);
+          sse_step_samples(a.k.obj_abs, [&](auto kind) {
+            for (int c0 = 0; c0 < n; c0 += 64) {
+              if (c0 + lane < n) {
+                const int idx = o + c0 + lane;
+                const double tk = a.k.t_eval[idx];
+                double vk;
+                if (vtb) vk = vtb[idx];
+                else protocol_v(a.k, pvb, tk, vk);
+                sse_sample_term<S, D, decltype(kind)::value>(a, cb, interp_x<S>(tk, t0b, den, rden), vk, refb[idx], gb, P);
+              }
             }
-          }
+          });
         } else {
         const S *__restrict__ gyb = reinterpret_cast<const S *>(a.grad_y) + (size_t)tr * Nt * D;
         for (int c0 = 0; c0 < n; c0 += 64) {
@@ -302,7 +304,7 @@
           if (a.v_tab) v0 = a.v_tab[(size_t)pidx * Nt];
           else protocol_v(a.k, pv, a.k.t_eval[0], v0);
           double dr[D];
-          const double gr = 2.0 * a.grad_sse[traj] * sse_residual<S, D>(a, y0s, v0, a.sse_ref[(size_t)pidx * Nt], dr);
+          const double gr = residual_weight(sse_residual<S, D>(a, y0s, v0, a.sse_ref[(size_t)pidx * Nt], dr), a.grad_sse[traj], a.k.obj_abs);
 #pragma unroll
           for (int d = 0; d < D; ++d) s0[d] = gr * dr[d];
         }

@@ -131,6 +131,20 @@ template <int N> __device__ __forceinline__ void residual_terms(double (&rr)[N],
   }
 }
 
+// ... and in the gradient: d term / d rr times the upstream scalar g = dL/dsum[b], the adjoint weight of the sample's residual.
+//   obj_abs == 0   (2 g) rr, in this order: the bits the backward sweep formed before it knew a second kind
+//   obj_abs == 1   g sign(rr), with sign(0) = 0 and sign(NaN) = NaN as torch.abs's backward has them (rr itself is returned for
+//                  both: g * (+-0) is the zero, g * NaN the NaN)
+// The sweeps pass obj_abs as a literal from either side of ONE wave-uniform branch per step and trajectory (sse_step_samples,
+// ionode_grad.hpp), so a sample pays no select; the sample-0 term, once per trajectory, passes KArgs::obj_abs itself.
+__device__ __forceinline__ double residual_weight(double rr, double g, int obj_abs) {
+  if (__builtin_expect(obj_abs != 0, 0)) {
+    const double sg = rr > 0.0 ? 1.0 : (rr < 0.0 ? -1.0 : rr);
+    return g * sg;
+  }
+  return (2.0 * g) * rr;
+}
+
 // ---- one step's interpolant, wave-uniform, as an emission loop holds it ----
 template <typename S, int D> struct Interp {
   using R = InterpRow<D>;

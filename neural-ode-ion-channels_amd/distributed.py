@@ -107,3 +107,32 @@ def sharded_mean_abs_loss_fused(solve_shard, n_traj, n_out, group=None):
         raise ValueError(f"solve_shard({lo}, {hi}) returned shape {tuple(sae.shape)}, expected {(hi - lo,)}")
     s, c = allreduce_sum_count(sae.sum(), (hi - lo) * n_out, group=group)
     return s / c
+
+
+def sharded_mean_abs_loss_fused_s1(solve_shard, leaves, n_traj, n_out, group=None):
+    """sharded_mean_abs_loss_fused WITH its gradient: (loss, [dloss/dleaf for leaf in leaves]), the reference's training loss
+    torch.mean(torch.abs(pred_yo - data)) (train-s1.py:329) over `n_traj` trajectories of `n_out` samples sharded over the ranks.
+
+    solve_shard(lo, hi) -> this rank's DIFFERENTIABLE [hi - lo] fused sums of absolute residuals (grad.sum_of_abs), whose graph
+    reaches `leaves` (tensors that require grad and that every rank holds whole: shared weights, shared rate parameters).  The global
+    mean comes from one allreduce_sum_count; the rank's share sum(sae) / (n_traj * n_out) is backpropagated, and the leaves' gradients
+    are summed over the ranks with grad.allreduce_gradients, one bucket.  A leaf the rank's shard does not reach (an empty shard)
+    contributes zeros.  A failed trajectory's inf makes the loss inf; its gradient rows are zero (grad.sum_of_abs).
+    """
+    import torch.distributed as dist
+    from . import grad
+    if dist.is_available() and dist.is_initialized():
+        rank, world = dist.get_rank(group), dist.get_world_size(group)
+    else:
+        rank, world = 0, 1
+    lo, hi = shard_bounds(n_traj, rank, world)
+    sae = solve_shard(lo, hi)
+    if tuple(sae.shape) != (hi - lo,):
+        raise ValueError(f"solve_shard({lo}, {hi}) returned shape {tuple(sae.shape)}, expected {(hi - lo,)}")
+    s, c = allreduce_sum_count(sae.detach().sum(), (hi - lo) * n_out, group=group)
+    leaves = list(leaves)
+    grads = [None] * len(leaves)
+    if hi > lo and sae.requires_grad:
+        grads = torch.autograd.grad(sae.sum() / float(n_traj * n_out), leaves, allow_unused=True)
+    grads = [torch.zeros_like(leaf) if g is None else g for leaf, g in zip(leaves, grads)]
+    return s / c, grad.allreduce_gradients(grads, group=group)

@@ -21,9 +21,13 @@ sum_of_squares: the fused objective sse[b] = sum_k (i_k - ref_k)^2 with its grad
 models: the one-phase sweep with the seed formed in the kernel (ionode_dopri5_backward_sse).  NN models: the two-phase sweep above
 without grad_y -- ionode_dopri5_backward_sse_gc (csrc/ionode_grad_gc.hpp) forms each chunk's interpolant-coefficient adjoints and the
 sample-0 term, ionode_dopri5_backward_recompute_sse / _sweep_sse are the recompute and walk launches that take them.
-Both routes are one autograd Function each (_Solve, _SumOfSquares) over the same three pieces: _forward_with_checkpoints, _backward
-(failed trajectories masked, rows zeroed) and the chunk loop _sweep, which calls the seven sweep entry points through
-capi.sweep_launch with every buffer named (capi.SWEEP_BUFFERS).
+sum_of_abs: the same with sae[b] = sum_k |i_k - ref_k|, Nt times the reference's loss torch.mean(torch.abs(pred_yo - data)) (train-s1.py:329,
+train-d1.py:305, train-r1.py:275) -- the same forward (objective="sae"), the same launches: the kind travels in cfg["objective"] to
+ionode_objective_backward / ionode_objective_backward_gc (capi.OBJECTIVE_BUFFERS), the two entry points that form the residuals'
+weights (2 g r or g sign(r)) and with the squares' kind ARE _sse / _sse_gc; the recompute, the walk and the reduce never see a residual.
+Both routes are one autograd Function each (_Solve, _FusedObjective) over the same three pieces: _forward_with_checkpoints, _backward
+(failed trajectories masked, rows zeroed) and the chunk loop _sweep, which calls the sweep entry points through capi.sweep_launch /
+capi.objective_launch with every buffer named (capi.SWEEP_BUFFERS, capi.OBJECTIVE_BUFFERS).
 There is no CPU fallback: without libionode.so or a HIP device every call raises.
 """
 import ctypes as C
@@ -82,7 +86,7 @@ def stable_step_cap(model, params, prot_v, v_oob=-80.0, safety=3.0):
 
 def _forward_with_checkpoints(ctx, weights_flat, params, y0, cfg, objective):
     """The forward of both autograd Functions: capi.dopri5 with the packed image of weights_flat (None: a closed-form model), cfg's
-    keywords and accepted-step checkpoints; objective: the fused sum of squares (sse_ref, obs_*; no state trace) instead of the states.
+    keywords and accepted-step checkpoints; objective: the fused objective of kind cfg["objective"] (sse_ref, obs_*; no state trace) instead of the states.
     The [B, cap, record] checkpoint buffer is sized by ckpt_cap / ckpt_budget_bytes and regrown (the forward runs again) until the steps
     of every trajectory that SUCCEEDED fit.  Saves what _backward reads on ctx and returns capi.dopri5's result."""
     dev = y0.device
@@ -98,7 +102,8 @@ def _forward_with_checkpoints(ctx, weights_flat, params, y0, cfg, objective):
               max_total_steps=cfg["max_total_steps"], max_step=cfg.get("max_step", 0.0), tile_waves=cfg.get("tile_waves", 0),
               t_eval_hint=cfg.get("t_eval_hint", "auto"))
     if objective:
-        kw.update(obs_g=cfg["obs_g"], obs_e=cfg["obs_e"], obs_open_state_only=cfg["obs_open_state_only"], sse_ref=cfg["sse_ref"], states=False)
+        kw.update(obs_g=cfg["obs_g"], obs_e=cfg["obs_e"], obs_open_state_only=cfg["obs_open_state_only"], sse_ref=cfg["sse_ref"], states=False,
+                  objective=cfg["objective"])
     cap = int(cfg.get("ckpt_cap") or DEFAULT_CKPT_CAP)
     limit = _bounded_budget(cfg.get("ckpt_budget_bytes"), DEFAULT_CKPT_BUDGET, dev, 0.6)
     row_bytes = B * capi.ckpt_record_doubles(D) * 8
@@ -153,9 +158,9 @@ def plan_backward_chunks(n_iter, tiles, record_floats, packet_doubles, budget, n
     return chunk, n_buf, [(it0, min(n_iter, it0 + chunk)) for it0 in range(0, n_iter, chunk)]
 
 
-def _resolve_max_step(model, params, prot_v, v_oob, max_step):
-    """max_step of solve / sum_of_squares as a number: "auto" = stable_step_cap(); warns (at the user's call: two frames up) when
-    the rate parameters require grad and no cap is set."""
+def _resolve_max_step(model, params, prot_v, v_oob, max_step, frames=2):
+    """max_step of solve / sum_of_squares / sum_of_abs as a number: "auto" = stable_step_cap(); warns (at the user's call: `frames`
+    frames up) when the rate parameters require grad and no cap is set."""
     if isinstance(max_step, str):
         if max_step != "auto":
             raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
@@ -165,7 +170,7 @@ def _resolve_max_step(model, params, prot_v, v_oob, max_step):
         warnings.warn("gradients w.r.t. the rate parameters through an UNCAPPED dopri5 solve: at equilibria dopri5 accepts steps with "
                       "h*lambda >> 1 whose exact derivative amplifies rounding noise without bound (|dL/dp| ~ 1e36 on long holds, "
                       "DESIGN.md 5.4).  Pass max_step='auto' (= 3 / lambda_max of the rate constants, grad.stable_step_cap) or a "
-                      "value in ms; the forward values then follow the capped step sequence.", RuntimeWarning, stacklevel=3)
+                      "value in ms; the forward values then follow the capped step sequence.", RuntimeWarning, stacklevel=frames + 1)
     return max_step
 
 
@@ -221,15 +226,15 @@ class _Solve(torch.autograd.Function):
         return _backward(ctx, gy, fused=False)
 
 
-class _SumOfSquares(torch.autograd.Function):
-    """sse[B] = sum_k (i_k - sse_ref[protocol][k])^2 of the fused forward; differentiable in (weights_flat, params, y0).  Nothing of size
-    [B, Nt] is ever allocated: the forward writes checkpoints and sse_out (no state trace), the backward sweeps with the [B] upstream
-    gradient."""
+class _FusedObjective(torch.autograd.Function):
+    """The fused forward's per-trajectory sums [B] of kind cfg["objective"]: "sse", sum_k (i_k - sse_ref[protocol][k])^2, or "sae",
+    sum_k |i_k - sse_ref[protocol][k]|; differentiable in (weights_flat, params, y0).  Nothing of size [B, Nt] is ever allocated: the
+    forward writes checkpoints and sse_out (no state trace), the backward sweeps with the [B] upstream gradient."""
 
     @staticmethod
     def forward(ctx, weights_flat, params, y0, cfg):
         r = _forward_with_checkpoints(ctx, weights_flat, params, y0, cfg, objective=True)
-        return r["sse"], r["status"]
+        return r[cfg["objective"]], r["status"]
 
     @staticmethod
     def backward(ctx, g_sse, _gstatus):
@@ -237,8 +242,8 @@ class _SumOfSquares(torch.autograd.Function):
 
 
 def _backward(ctx, g, fused):
-    """The backward of both Functions: g is the upstream dL/dy [B, Nt, D], or (fused) dL/dsse [B].  Failed trajectories (status != 0:
-    their rows of y are NaN-filled, their sse is inf) carry no gradient: their upstream rows are zeroed (a caller's unmasked loss would
+    """The backward of both Functions: g is the upstream dL/dy [B, Nt, D], or (fused) dL/dsum [B].  Failed trajectories (status != 0:
+    their rows of y are NaN-filled, their sum is inf) carry no gradient: their upstream rows are zeroed (a caller's unmasked loss would
     otherwise feed NaN into the sweep), they replay no steps, and their rows of dL/dp and dL/dy0 are zero."""
     cfg, desc = ctx.cfg, ctx.desc
     params, ckpt, stats, status = ctx.saved_tensors
@@ -256,9 +261,9 @@ def _backward(ctx, g, fused):
 
 
 def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, g, fused):
-    """The backward sweep's chunk loop.  g: the upstream dL/dy [B, Nt, D] in the state dtype, or (fused) dL/dsse [B] fp64 of the
-    sum-of-squares objective -- closed-form models: one launch of ionode_dopri5_backward_sse; NN models: two-phase only, per chunk
-    ionode_dopri5_backward_sse_gc forms the packets' G_c on the phase-A stream and the products run without grad_y.  n_acc [B] int32:
+    """The backward sweep's chunk loop.  g: the upstream dL/dy [B, Nt, D] in the state dtype, or (fused) dL/dsum [B] fp64 of the
+    fused objective of kind cfg["objective"] -- closed-form models: one launch of ionode_objective_backward; NN models: two-phase only,
+    per chunk ionode_objective_backward_gc forms the packets' G_c on the phase-A stream and the products run without grad_y.  n_acc [B] int32:
     accepted steps to replay (0 for failed trajectories).  Returns (padded partial weight gradient fp64 | None, dL/dp [B, NPAR], dL/dy0
     [B, D]), the rows of failed trajectories not yet zeroed."""
     dev = params.device
@@ -273,7 +278,7 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, g, fused):
     # the walk wrote) runs on a third stream.  Records and packets are double-buffered.
     two_phase = bool(cfg.get("two_phase", os.environ.get("IONODE_GRAD_ONE_PHASE", "0") != "1")) and w_np is not None
     if fused and w_np is not None and not two_phase:
-        raise capi.IonodeError("the fused sum-of-squares sweep of the NN models is two-phase only: use grad.solve for the one-phase sweep")
+        raise capi.IonodeError("the fused objective's sweep of the NN models is two-phase only: use grad.solve for the one-phase sweep")
     desc.ckpt, desc.ckpt_cap = ckpt.data_ptr(), ckpt.shape[1]
     gc_desc = desc
     if fused and two_phase and desc.v_at_outputs is None and 4 * desc.n_prot <= desc.n_traj:
@@ -309,6 +314,7 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, g, fused):
     # the entry points' buffers by name (capi.SWEEP_BUFFERS): what all seven take, what the launches that run the net add, the adjoint
     shared = dict(prot_v=cfg["prot_v"], prot_t=cfg.get("prot_t"), prot_of_traj=cfg.get("prot_of_traj"), t_eval=cfg["t_eval"], n_accepted=n_acc)
     net = dict(shared, grad_image=image, params=params)
+    kind = capi.objective_kind(cfg["objective"]) if fused else None   # the two launches that form the residuals' weights take it
     adjoint = dict(state=state, grad_params=g_params, grad_y0=g_y0)
 
     def phase_a(k):
@@ -317,8 +323,8 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, g, fused):
         if free[b] is not None:
             pre.wait_event(free[b])
         if fused:   # G_c of the objective (one wavefront per trajectory and step), then the products without grad_y: same stream, same packets
-            capi.sweep_launch("ionode_dopri5_backward_sse_gc", gc_desc, it0, it1, n_iter, pre, grad_sse=g, packets=packets[b],
-                              sse_grad_y0=sse_y0, **shared)
+            capi.objective_launch("ionode_objective_backward_gc", gc_desc, kind, it0, it1, n_iter, pre, grad_sse=g, packets=packets[b],
+                                  sse_grad_y0=sse_y0, **shared)
             capi.sweep_launch("ionode_dopri5_backward_recompute_sse", desc, it0, it1, n_iter, pre, records=records[b], packets=packets[b], **net)
         else:
             capi.sweep_launch("ionode_dopri5_backward_recompute", desc, it0, it1, n_iter, pre, grad_y=g, records=records[b],
@@ -346,7 +352,7 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, g, fused):
             if free[b] is not None:
                 main.wait_event(free[b])
             if fused:   # closed-form models: the seed is formed in the kernel; one launch (plan_backward_chunks: nothing to buffer)
-                capi.sweep_launch("ionode_dopri5_backward_sse", desc, it0, it1, n_iter, main, params=params, grad_sse=g, **shared, **adjoint)
+                capi.objective_launch("ionode_objective_backward", desc, kind, it0, it1, n_iter, main, params=params, grad_sse=g, **shared, **adjoint)
             else:
                 capi.sweep_launch("ionode_dopri5_backward", desc, it0, it1, n_iter, main, grad_y=g, records=rec, **net, **adjoint)
         swept = torch.cuda.Event()
@@ -465,7 +471,7 @@ def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, p
     their upstream values are ignored and their dL/dp, dL/dy0 rows are zero.
 
     Neither the states nor the current trace nor dL/dy is ever materialised: the forward writes accepted-step checkpoints and
-    the per-trajectory sums only, and the backward sweep (ionode_dopri5_backward_sse) re-evaluates every output sample from the
+    the per-trajectory sums only, and the backward sweep (ionode_objective_backward, the squares' kind) re-evaluates every output sample from the
     checkpoints and forms dL/dy_k in the kernel.  Memory: the checkpoints (sized, regrown and bounded by ckpt_cap /
     ckpt_budget_bytes as in grad.solve) plus O(B).  The output grid must be uniform (the fused forward's output cursor); for any
     other t_eval use the materialised route, grad.solve followed by the sum of squares in torch.  max_step: as grad.solve.
@@ -473,22 +479,62 @@ def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, p
     NN-f / NN-d: weights_flat [n] fp32 (reference state-dict order, as grad.solve's; it may require grad), mlp_layers, mlp_width,
     weights_key (the weight images' cache key) and record_budget_bytes as in grad.solve; params [B, 8], y0 [B, 2].  The result is
     differentiable in weights_flat, params and y0.  The backward is grad.solve's two-phase sweep with the same chunking, streams and
-    reduction; per chunk ionode_dopri5_backward_sse_gc re-evaluates the steps' output samples from the checkpoints and hands their
+    reduction; per chunk ionode_objective_backward_gc re-evaluates the steps' output samples from the checkpoints and hands their
     sums to the walk, and the vector-Jacobian products run without an output gradient.  Memory: the checkpoints, the chunk's records
     and packets (record_budget_bytes), O(B) -- nothing of size [B, Nt].  This route is two-phase only: with two_phase=False, or
     IONODE_GRAD_ONE_PHASE=1 in the environment, it raises; the one-phase sweep serves the materialised route (grad.solve)."""
+    return _fused_objective("sse", model, params, prot_v, y0, t_eval, sse_ref, prot_t=prot_t, prot_t0=prot_t0, prot_dt=prot_dt,
+                            prot_of_traj=prot_of_traj, obs_g=obs_g, obs_e=obs_e, obs_open_state_only=obs_open_state_only, rtol=rtol, atol=atol,
+                            v_oob=v_oob, max_steps=max_steps, max_total_steps=max_total_steps, max_step=max_step, ckpt_cap=ckpt_cap,
+                            ckpt_budget_bytes=ckpt_budget_bytes, weights_flat=weights_flat, mlp_layers=mlp_layers, mlp_width=mlp_width,
+                            weights_key=weights_key, record_budget_bytes=record_budget_bytes, two_phase=two_phase)
+
+
+def sum_of_abs(model, params, prot_v, y0, t_eval, sae_ref, *, prot_t=None, prot_t0=0.0, prot_dt=1.0, prot_of_traj=None,
+               obs_g=1.0, obs_e=-86.0, obs_open_state_only=False, rtol=1e-7, atol=1e-9, v_oob=-80.0, max_steps=0,
+               max_total_steps=0, max_step=0.0, ckpt_cap=None, ckpt_budget_bytes=None, weights_flat=None, mlp_layers=0, mlp_width=0,
+               weights_key=None, record_budget_bytes=None, two_phase=None):
+    """Fused sum-of-absolute-errors objective with its gradient: the reference's loss torch.mean(torch.abs(pred_yo - data))
+    (train-s1.py:329, train-d1.py:305, train-r1.py:275) times the sample count, differentiated through the solve as its
+    `odeint_adjoint` import promises -- all four models, as grad.sum_of_squares.
+
+    sae[b] = sum_k |i_k - sae_ref[protocol(b)][k]|, i_k and k as in grad.sum_of_squares: the objective of
+    batched.solve(sse_ref=..., objective="sae", states=False), bit for bit.  Arguments, shapes and dtypes are grad.sum_of_squares';
+    sae_ref [P, Nt] fp64 holds the reference currents.  Returns (sae [B] fp64, status [B] int32), differentiable in params and y0
+    (and in weights_flat for NN-f / NN-d): the exact derivative of the discretisation the forward executed, with
+    d|r|/dr = sign(r) and sign(0) = 0, the subgradient torch.abs's backward takes.  Failed trajectories (status != 0) give
+    sae = inf; their upstream values are ignored and their dL/dp, dL/dy0 rows are zero.  The mean absolute error of a batch is
+    sae.sum() / (B * Nt).
+
+    The launches, the memory (checkpoints plus O(B), and a chunk's records and packets for the NN models: nothing of size [B, Nt]),
+    the uniform output grid, max_step and the two-phase-only rule of the NN models are grad.sum_of_squares': one body serves both, the
+    kind travels to ionode_objective_backward / ionode_objective_backward_gc, where a sample's adjoint weight is
+    dL/dsae[b] sign(r_k) instead of 2 dL/dsse[b] r_k.  For any other t_eval use the materialised route, grad.solve followed by the
+    absolute values in torch."""
+    return _fused_objective("sae", model, params, prot_v, y0, t_eval, sae_ref, prot_t=prot_t, prot_t0=prot_t0, prot_dt=prot_dt,
+                            prot_of_traj=prot_of_traj, obs_g=obs_g, obs_e=obs_e, obs_open_state_only=obs_open_state_only, rtol=rtol, atol=atol,
+                            v_oob=v_oob, max_steps=max_steps, max_total_steps=max_total_steps, max_step=max_step, ckpt_cap=ckpt_cap,
+                            ckpt_budget_bytes=ckpt_budget_bytes, weights_flat=weights_flat, mlp_layers=mlp_layers, mlp_width=mlp_width,
+                            weights_key=weights_key, record_budget_bytes=record_budget_bytes, two_phase=two_phase)
+
+
+def _fused_objective(objective, model, params, prot_v, y0, t_eval, sse_ref, *, prot_t, prot_t0, prot_dt, prot_of_traj, obs_g, obs_e,
+                     obs_open_state_only, rtol, atol, v_oob, max_steps, max_total_steps, max_step, ckpt_cap, ckpt_budget_bytes, weights_flat,
+                     mlp_layers, mlp_width, weights_key, record_budget_bytes, two_phase):
+    """The one body of sum_of_squares ("sse") and sum_of_abs ("sae"): argument checks, cfg, _FusedObjective."""
+    who = "grad.sum_of_squares" if objective == "sse" else "grad.sum_of_abs"
     nn = model in (capi.MODEL_NNF, capi.MODEL_NND)
     if not nn and model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
         raise NotImplementedError("unknown model")
     if nn and weights_flat is None:
-        raise capi.IonodeError("grad.sum_of_squares: only the closed-form models have no weights; an NN model needs weights_flat, "
+        raise capi.IonodeError(f"{who}: only the closed-form models have no weights; an NN model needs weights_flat, "
                                "mlp_layers and mlp_width")
     if not nn and weights_flat is not None:
         raise capi.IonodeError("the closed-form models have no MLP: pass weights_flat=None")
     if nn and (os.environ.get("IONODE_GRAD_ONE_PHASE", "0") == "1" or (two_phase is not None and not two_phase)):
-        raise capi.IonodeError("grad.sum_of_squares: the fused sweep of the NN models is two-phase only (two_phase=False or "
-                               "IONODE_GRAD_ONE_PHASE=1 asks for the one-phase sweep); for that use grad.solve and form the sum of squares in torch")
-    max_step = _resolve_max_step(model, params, prot_v, v_oob, max_step)
+        raise capi.IonodeError(f"{who}: the fused sweep of the NN models is two-phase only (two_phase=False or "
+                               "IONODE_GRAD_ONE_PHASE=1 asks for the one-phase sweep); for that use grad.solve and form the sum in torch")
+    max_step = _resolve_max_step(model, params, prot_v, v_oob, max_step, frames=3)
     if not (isinstance(y0, torch.Tensor) and y0.is_cuda):
         raise capi.IonodeError("no HIP tensors: the integrator and its backward sweep have no CPU path")
     D = capi.n_state(model)
@@ -496,13 +542,13 @@ def sum_of_squares(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, p
         raise capi.IonodeError(f"params [B, {capi.n_params(model)}] and y0 [B, {D}] expected")
     hint = uniform_grid_hint(t_eval)
     if hint is None:
-        raise capi.IonodeError("grad.sum_of_squares needs a uniform output grid t_eval (the fused objective's output cursor); for "
-                               "other grids use the materialised route: grad.solve, then the sum of squares of the current in torch")
+        raise capi.IonodeError(f"{who} needs a uniform output grid t_eval (the fused objective's output cursor); for "
+                               "other grids use the materialised route: grad.solve, then the sum over the current's residuals in torch")
     cfg = dict(model=model, prot_v=prot_v, prot_t=prot_t, prot_t0=float(prot_t0), prot_dt=float(prot_dt), t_eval=t_eval,
                prot_of_traj=None if prot_of_traj is None else torch.as_tensor(prot_of_traj, device=y0.device).to(torch.int32).contiguous(),
                rtol=float(rtol), atol=float(atol), v_oob=float(v_oob), max_steps=int(max_steps), max_total_steps=int(max_total_steps),
                max_step=float(max_step), obs_g=float(obs_g), obs_e=float(obs_e), obs_open_state_only=bool(obs_open_state_only),
                t_eval_hint=hint, sse_ref=sse_ref, ckpt_cap=ckpt_cap, ckpt_budget_bytes=ckpt_budget_bytes,
                mlp_layers=int(mlp_layers) if nn else 0, mlp_width=int(mlp_width) if nn else 0, weights_key=weights_key,
-               record_budget_bytes=record_budget_bytes, two_phase=True)
-    return _SumOfSquares.apply(weights_flat, params, y0.contiguous(), cfg)
+               record_budget_bytes=record_budget_bytes, two_phase=True, objective=objective)
+    return _FusedObjective.apply(weights_flat, params, y0.contiguous(), cfg)

@@ -148,9 +148,40 @@ def population_sum_of_squares_s1(candidates, protocols_v, data_i, t_eval, *, bas
     all-gather carries [C, 1 + len(free)].  `solver` (tests only): a stand-in with grad.sum_of_squares' signature, returning a
     differentiable (sse, status), so the sharding / all-gather logic can run under gloo without a GPU.
     """
+    return _population_error_s1("sse", candidates, protocols_v, data_i, t_eval, base_params=base_params, free=free, prot_t0=prot_t0,
+                                prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e,
+                                obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=max_step, group=group,
+                                device=device, solver=solver, cost=cost, model=model)
+
+
+def population_mean_abs_error_s1(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), prot_t0=0.0,
+                                 prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
+                                 obs_open_state_only=False, max_total_steps=1_000_000, max_step="auto", group=None, device=None,
+                                 solver=None, cost=None, model=capi.MODEL_HH2):
+    """Mean absolute error of every candidate AND its gradient with respect to the free parameters: the reference's loss
+    torch.mean(torch.abs(pred_yo - data)) (train-s1.py:329, train-d1.py:305) differentiated through the solve, for a whole
+    population -- the sibling of population_sum_of_squares_s1, as population_mean_abs_error is of population_sum_of_squares.
+
+    Arguments, models, sharding, the population-wide "auto" step cap and the all-gather as population_sum_of_squares_s1.  Returns
+    (mae [C] fp64, dmae [C, len(free)] fp64) on the device: mae[c] is the mean of |i - data| over the candidate's P * Nt samples --
+    population_mean_abs_error's value -- and dmae[c, j] = d mae[c] / d candidates[c, j] (grad.sum_of_abs: fused forward + fused
+    backward, sign(0) = 0, no trace of size [C * P, Nt] is written).  A candidate any of whose solves failed gets mae = inf and a ZERO
+    gradient row.  `solver` (tests only): a stand-in with grad.sum_of_abs' signature, returning a differentiable (sae, status).
+    """
+    return _population_error_s1("sae", candidates, protocols_v, data_i, t_eval, base_params=base_params, free=free, prot_t0=prot_t0,
+                                prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e,
+                                obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=max_step, group=group,
+                                device=device, solver=solver, cost=cost, model=model)
+
+
+def _population_error_s1(kind, candidates, protocols_v, data_i, t_eval, *, base_params, free, prot_t0, prot_dt, y0, state_dtype, obs_g,
+                         obs_e, obs_open_state_only, max_total_steps, max_step, group, device, solver, cost, model):
+    """The one body of population_sum_of_squares_s1 (kind "sse": [C] sums) and population_mean_abs_error_s1 (kind "sae": [C] means),
+    each with its gradient: the population-wide step cap, shard, fused solve and sweep, reduce each candidate's P sweeps, all-gather."""
+    who = "population_sum_of_squares_s1" if kind == "sse" else "population_mean_abs_error_s1"
     import torch.distributed as dist
     if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
-        raise capi.IonodeError("population_sum_of_squares_s1: HH 2-state and 6-state models only")
+        raise capi.IonodeError(f"{who}: HH 2-state and 6-state models only")
     D, npar = (6, 12) if model == capi.MODEL_MARKOV6 else (2, 8)
     free = [int(f) for f in free]
     cand = np.asarray(candidates, dtype=np.float64).reshape(-1, len(free))
@@ -166,7 +197,7 @@ def population_sum_of_squares_s1(candidates, protocols_v, data_i, t_eval, *, bas
         else distributed.shard_bounds_by_cost(cost, world)
     lo, hi = bounds[rank]
     dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
-    solve = grad.sum_of_squares if solver is None else solver
+    solve = (grad.sum_of_squares if kind == "sse" else grad.sum_of_abs) if solver is None else solver
     params_all = np.tile(base, (C, 1))
     params_all[:, free] = cand
     if isinstance(max_step, str):
@@ -191,6 +222,9 @@ def population_sum_of_squares_s1(candidates, protocols_v, data_i, t_eval, *, bas
         ok = (status.reshape(n, P) == 0).all(dim=1)
         err = sse.detach().reshape(n, P).sum(dim=1)
         gc = gp.reshape(n, P, npar).sum(dim=1)[:, free]
+        if kind == "sae":   # the mean over the candidate's P * Nt samples, and its gradient
+            n_samples = P * np.asarray(data_i).shape[1]
+            err, gc = err / n_samples, gc / n_samples
         out[:, 0] = torch.where(ok, err, torch.full_like(err, float("inf")))
         out[:, 1:] = torch.where(ok[:, None], gc, torch.zeros_like(gc))
     if world > 1:
