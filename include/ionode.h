@@ -154,7 +154,8 @@ int ionode_mlp_pack(const float *state_dict_flat, int32_t mlp_layers, int32_t ml
  *   stream        hipStream_t (NULL = default stream)
  *
  * Returns IONODE_OK once the kernel is enqueued; per-trajectory failures are reported in status[]
- * (their remaining outputs are NaN), never as a return code.
+ * (their remaining outputs are NaN), never as a return code.  d == NULL is IONODE_ERR_ARG ("null descriptor") here and on
+ * ionode_dopri5_deferred / _composed / _objective, which share this entry point's checks (earlier builds dereferenced it).
  */
 int ionode_dopri5(const ionode_desc *d, const float *mlp_packed, const double *params, const double *prot_v,
                   const double *prot_t, const int32_t *prot_of_traj, const void *y0, const double *t_eval,

@@ -23,19 +23,6 @@ STATUS_TEXT = {
 }
 ABI_VERSION = 10
 
-EXPORTS = (
-    "ionode_abi_version", "ionode_last_error", "ionode_mlp_packed_floats", "ionode_mlp_pack",
-    "ionode_launch_geometry", "ionode_kernel_name", "ionode_last_kernel_name", "ionode_lane_wise_from", "ionode_dopri5", "ionode_protocol_at_outputs",
-    "ionode_grad_image_floats", "ionode_grad_pack", "ionode_grad_record_floats", "ionode_dopri5_backward", "ionode_dopri5_backward_sse",
-    "ionode_grad_packet_doubles", "ionode_dopri5_backward_recompute", "ionode_dopri5_backward_sweep",
-    "ionode_dopri5_backward_sse_gc", "ionode_dopri5_backward_recompute_sse", "ionode_dopri5_backward_sweep_sse",
-    "ionode_grad_partial_floats", "ionode_grad_reduce", "ionode_grad_reduce_unit", "ionode_grad_reduce_slabs", "ionode_grad_last_error",
-    "ionode_regress_step", "ionode_adam_step", "ionode_image_refresh", "ionode_regress_plan",
-    "ionode_dense_defer_plan", "ionode_dense_tail_plan", "ionode_dopri5_deferred",
-    "ionode_compose_plan", "ionode_compose_order", "ionode_compose_order_host", "ionode_dopri5_composed", "ionode_compose_tail_plan",
-    "ionode_dopri5_objective", "ionode_objective_backward", "ionode_objective_backward_gc",
-)
-
 # the kind of the fused objective (include/ionode.h IONODE_OBJECTIVE_*): what a residual adds to its trajectory's sum
 OBJECTIVE_SSE, OBJECTIVE_SAE = 0, 1
 OBJECTIVE_KINDS = {"sse": OBJECTIVE_SSE, "sae": OBJECTIVE_SAE}
@@ -95,6 +82,49 @@ class IonodeError(RuntimeError):
     pass
 
 
+# Every symbol of include/ionode.h: name -> (restype, argtypes); lib() applies the table, EXPORTS is its keys.
+_D, _P, _I32, _I64, _F32 = C.POINTER(IonodeDesc), C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_SOLVE = [_D] + [_P] * 12   # ionode_dopri5: d, mlp_packed .. stats, stream -- the solve family's common prefix
+_REDUCE = [_I32, _I32, _P, _I64, _I32, _P, _P]
+PROTOTYPES = {
+    "ionode_abi_version": (_I32, []),
+    "ionode_last_error": (C.c_char_p, []),
+    "ionode_mlp_packed_floats": (C.c_size_t, [_I32, _I32]),
+    "ionode_mlp_pack": (C.c_int, [_P, _I32, _I32, _P]),
+    "ionode_launch_geometry": (C.c_int, [_D, C.POINTER(_I32 * 4)]),
+    "ionode_kernel_name": (C.c_char_p, [_D]),
+    "ionode_last_kernel_name": (C.c_char_p, []),
+    "ionode_lane_wise_from": (_I32, [_I32, _I32]),
+    "ionode_dopri5": (C.c_int, _SOLVE),
+    "ionode_dopri5_deferred": (C.c_int, _SOLVE + [_P, _I64]),                    # + workspace, workspace_bytes
+    "ionode_dopri5_composed": (C.c_int, _SOLVE + [_P, _I64, _I32]),              # + cost_source
+    "ionode_dopri5_objective": (C.c_int, _SOLVE + [_P, _I64, _I32, _I32]),       # + objective
+    "ionode_protocol_at_outputs": (C.c_int, [_D] + [_P] * 5),
+    "ionode_dense_defer_plan": (C.c_int, [_D, _I32, C.POINTER(_I64 * 2)]),
+    "ionode_dense_tail_plan": (C.c_int, [_D, _I32, C.POINTER(_I64 * 2)]),
+    "ionode_compose_tail_plan": (C.c_int, [_D, _I32, _I32, C.POINTER(_I64 * 2)]),
+    "ionode_compose_plan": (C.c_int, [_D, _I32, C.POINTER(_I32 * 2)]),
+    "ionode_compose_order": (C.c_int, [_P, _I32, _I64, _I32, _P, _P]),
+    "ionode_compose_order_host": (C.c_int, [_P, _I32, _P]),
+    "ionode_grad_last_error": (C.c_char_p, []),
+    "ionode_grad_image_floats": (C.c_size_t, [_I32, _I32]),
+    "ionode_grad_record_floats": (C.c_size_t, [_I32, _I32]),
+    "ionode_grad_partial_floats": (C.c_size_t, [_I32, _I32]),
+    "ionode_grad_pack": (C.c_int, [_P, _I32, _I32, _P]),
+    "ionode_grad_packet_doubles": (C.c_size_t, []),
+    **{name: (C.c_int, [_D] + [_I32] * 3 + [_P] * (len(buffers) + 1)) for name, buffers in SWEEP_BUFFERS.items()},
+    **{name: (C.c_int, [_D] + [_I32] * 4 + [_P] * (len(buffers) + 1)) for name, buffers in OBJECTIVE_BUFFERS.items()},
+    "ionode_grad_reduce": (C.c_int, _REDUCE),
+    "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
+    "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),
+    "ionode_regress_step": (C.c_int, [_I32, _I32, _P, _P, _P, _P, _I32, _F32, _P, _P, _I32, _P]),
+    "ionode_regress_plan": (C.c_int, [_I32, _I32, C.POINTER(_I32 * 3)]),
+    "ionode_adam_step": (C.c_int, [_I32] * 4 + [_P] * 5 + [_F32] * 4 + [_I32, _P, _I32, _P]),
+    "ionode_image_refresh": (C.c_int, [_I32, _I32, _P, _P, _P, _P]),
+}
+EXPORTS = tuple(PROTOTYPES)
+
+
 def ckpt_record_doubles(D):
     """fp64 words of one accepted-step checkpoint record [t0, dt, oi, nout, y[D], k1..k7[D]] (csrc/ionode_grad_step.hpp CkptRecord)."""
     return 4 + 8 * D
@@ -119,73 +149,9 @@ def lib():
             raise IonodeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                               "(there is no CPU fallback for the integrator)")
         L = C.CDLL(LIB_PATH)
-        L.ionode_abi_version.restype = C.c_int32
-        L.ionode_last_error.restype = C.c_char_p
-        L.ionode_kernel_name.restype = C.c_char_p
-        L.ionode_kernel_name.argtypes = [C.POINTER(IonodeDesc)]
-        L.ionode_mlp_packed_floats.restype = C.c_size_t
-        L.ionode_mlp_packed_floats.argtypes = [C.c_int32, C.c_int32]
-        L.ionode_mlp_pack.restype = C.c_int
-        L.ionode_mlp_pack.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        L.ionode_launch_geometry.restype = C.c_int
-        L.ionode_launch_geometry.argtypes = [C.POINTER(IonodeDesc), C.POINTER(C.c_int32 * 4)]
-        L.ionode_dopri5.restype = C.c_int
-        L.ionode_dopri5.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 12
-        L.ionode_dopri5_deferred.restype = C.c_int
-        L.ionode_dopri5_deferred.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 13 + [C.c_int64]
-        L.ionode_dense_defer_plan.restype = C.c_int
-        L.ionode_dense_defer_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int64 * 2)]
-        L.ionode_dense_tail_plan.restype = C.c_int
-        L.ionode_dense_tail_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int64 * 2)]
-        L.ionode_compose_plan.restype = C.c_int
-        L.ionode_compose_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.POINTER(C.c_int32 * 2)]
-        L.ionode_compose_order.restype = C.c_int
-        L.ionode_compose_order.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-        L.ionode_dopri5_composed.restype = C.c_int
-        L.ionode_dopri5_composed.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 13 + [C.c_int64, C.c_int32]
-        L.ionode_dopri5_objective.restype = C.c_int
-        L.ionode_dopri5_objective.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 13 + [C.c_int64, C.c_int32, C.c_int32]
-        L.ionode_compose_tail_plan.restype = C.c_int
-        L.ionode_compose_tail_plan.argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.POINTER(C.c_int64 * 2)]
-        L.ionode_compose_order_host.restype = C.c_int
-        L.ionode_compose_order_host.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-        L.ionode_grad_last_error.restype = C.c_char_p
-        for fn in (L.ionode_grad_image_floats, L.ionode_grad_record_floats, L.ionode_grad_partial_floats):
-            fn.restype = C.c_size_t
-            fn.argtypes = [C.c_int32, C.c_int32]
-        L.ionode_grad_pack.restype = C.c_int
-        L.ionode_grad_pack.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
-        L.ionode_grad_packet_doubles.restype = C.c_size_t
-        L.ionode_grad_packet_doubles.argtypes = []
-        for name, buffers in SWEEP_BUFFERS.items():
-            getattr(L, name).restype = C.c_int
-            getattr(L, name).argtypes = [C.POINTER(IonodeDesc), C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * (len(buffers) + 1)
-        for name, buffers in OBJECTIVE_BUFFERS.items():
-            getattr(L, name).restype = C.c_int
-            getattr(L, name).argtypes = [C.POINTER(IonodeDesc)] + [C.c_int32] * 4 + [C.c_void_p] * (len(buffers) + 1)
-        L.ionode_grad_reduce.restype = C.c_int
-        L.ionode_grad_reduce.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-        L.ionode_grad_reduce_slabs.restype = C.c_int32
-        L.ionode_grad_reduce_slabs.argtypes = [C.c_int32, C.c_int32, C.c_int64]
-        L.ionode_grad_reduce_unit.restype = C.c_int
-        L.ionode_grad_reduce_unit.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p]
-        L.ionode_regress_step.restype = C.c_int
-        L.ionode_regress_step.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                          C.c_float, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-        L.ionode_regress_plan.restype = C.c_int
-        L.ionode_regress_plan.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_int32 * 3)]
-        L.ionode_adam_step.restype = C.c_int
-        L.ionode_adam_step.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                       C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int32,
-                                       C.c_void_p, C.c_int32, C.c_void_p]
-        L.ionode_image_refresh.restype = C.c_int
-        L.ionode_image_refresh.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.ionode_last_kernel_name.restype = C.c_char_p
-        L.ionode_last_kernel_name.argtypes = []
-        L.ionode_lane_wise_from.restype = C.c_int32
-        L.ionode_lane_wise_from.argtypes = [C.c_int32, C.c_int32]
-        L.ionode_protocol_at_outputs.restype = C.c_int
-        L.ionode_protocol_at_outputs.argtypes = [C.POINTER(IonodeDesc)] + [C.c_void_p] * 5
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         if L.ionode_abi_version() != ABI_VERSION:
             raise IonodeError("libionode.so ABI version mismatch; rebuild")
         _lib = L
@@ -196,13 +162,20 @@ def last_error():
     return lib().ionode_last_error().decode()
 
 
+def state_dict_floats(w, L, N):
+    """Floats of the reference's flat state dict of an (L, N) net -- W0[N][2], b0[N], L x (W[N][N], b[N]), wl[N], bl -- after checking
+    that the flat array `w` has that many."""
+    expect = 2 * N + N + L * (N * N + N) + N + 1
+    if w.size != expect:
+        raise IonodeError(f"state dict has {w.size} floats, (L={L}, N={N}) needs {expect}")
+    return expect
+
+
 def mlp_pack(state_dict_flat, mlp_layers, mlp_width):
     """Flat fp32 state dict (numpy, reference order) -> packed fp32 image (numpy) for upload."""
     w = np.ascontiguousarray(np.asarray(state_dict_flat, dtype=np.float32).reshape(-1))
     N, L = int(mlp_width), int(mlp_layers)
-    expect = 2 * N + N + L * (N * N + N) + N + 1
-    if w.size != expect:
-        raise IonodeError(f"state dict has {w.size} floats, (L={L}, N={N}) needs {expect}")
+    state_dict_floats(w, L, N)
     out = np.empty(lib().ionode_mlp_packed_floats(L, N), dtype=np.float32)
     rc = lib().ionode_mlp_pack(w.ctypes.data, L, N, out.ctypes.data)
     if rc != 0:
@@ -362,6 +335,138 @@ def _protocol_major(prot_of_traj):
     return hit[0]
 
 
+# ---- the steps of dopri5(), in the order it takes them ----
+
+def _grid_hint(desc, t_eval, t_eval_hint, t_eval_exact):
+    """Output-grid hint (t0, dt) into `desc`: a guess the kernel verifies against t_eval; "auto" derives it from the end points
+    (one tiny device->host read), None disables it (cooperative scan)."""
+    if isinstance(t_eval_hint, str) and t_eval_hint == "auto":
+        t_eval_hint = uniform_grid(t_eval)   # pass t_eval_hint=(t0, dt) to avoid its device->host read
+        if t_eval_hint is not None and t_eval_exact is None:
+            t_eval_exact = t_eval_hint[2] == 0.0
+    if t_eval_hint is not None and t_eval_hint[1] > 0:
+        desc.t_eval_t0_hint, desc.t_eval_dt_hint = float(t_eval_hint[0]), float(t_eval_hint[1])
+        if t_eval_exact is None:
+            # exactness is a CLAIM the kernel relies on: verify it here (one tiny device->host read) unless the caller did
+            k = torch.arange(desc.n_out, dtype=torch.float64, device=t_eval.device)
+            t_eval_exact = bool(torch.equal(t_eval, float(t_eval_hint[0]) + k * float(t_eval_hint[1])))
+        desc.t_eval_exact = int(bool(t_eval_exact))
+
+
+def _auto_order(model, mlp_width, prot_of_traj, P, B, traj_per_image):
+    """launch_order="auto" before any composition: protocol-major order, or None.  One trajectory per lane (64 per wavefront) from
+    these batch sizes on -- the dispatcher's crossovers (csrc/ionode_plan.hpp lane_wise_from): there the 64 lanes of a wavefront
+    should read ONE protocol."""
+    lane_from = int(lib().ionode_lane_wise_from(int(model), int(mlp_width or 0)))
+    if lane_from > 0 and prot_of_traj is not None and P > 1 and B >= lane_from and not traj_per_image:
+        return _protocol_major(prot_of_traj)
+    return None
+
+
+def _outputs(out, desc, shape, sdt, dev, states, current, stats, sse_ref, objective):
+    """The output tensors, from `out` where the caller passed them, else allocated: (y, sse, i, status, stats, stats came from the
+    caller).  The fused objective's pointers go into `desc`."""
+    B, Nt, D, P = shape
+    if out is None:
+        out = {}
+    y = out.get("y")
+    if y is None and states:
+        y = torch.empty((B, Nt, D), dtype=sdt, device=dev)
+    sse = None
+    if sse_ref is not None:  # fused objective: [P, Nt] reference currents -> per-trajectory sum of squared (absolute) residuals
+        _dev_ptr(sse_ref, torch.float64, "sse_ref", (P, Nt))
+        sse = out.get(objective)
+        if sse is None:
+            sse = torch.empty((B,), dtype=torch.float64, device=dev)
+        desc.sse_ref, desc.sse_out = sse_ref.data_ptr(), sse.data_ptr()
+    elif not states:
+        raise IonodeError("states=False needs sse_ref (something must be computed)")
+    i_out = out.get("i")
+    if current and i_out is None:
+        i_out = torch.empty((B, Nt), dtype=torch.float64, device=dev)
+    status = out.get("status")
+    if status is None:
+        status = torch.empty((B,), dtype=torch.int32, device=dev)
+    st = out.get("stats")
+    stats_from_caller = st is not None
+    if stats and st is None:
+        st = torch.empty((B, 4), dtype=torch.int64, device=dev)
+    return y, sse, i_out, status, st, stats_from_caller
+
+
+def _voltage_table(desc, v_at_outputs, prot_v, prot_t, t_eval, s):
+    """Closed-form current / objective epilogue: V(t_k) once per protocol instead of once per trajectory per sample ("auto": when
+    every protocol serves at least four trajectories; a [P, Nt] f64 tensor from an earlier call may be passed back in).  The table,
+    also set in `desc`, or None."""
+    vtab = None
+    if isinstance(v_at_outputs, str):
+        if 4 * desc.n_prot <= desc.n_traj:
+            vtab = protocol_at_outputs(desc, prot_v, prot_t, t_eval, stream=s)
+    else:
+        vtab = v_at_outputs
+        _dev_ptr(vtab, torch.float64, "v_at_outputs", (desc.n_prot, desc.n_out))
+    if vtab is not None:
+        desc.v_at_outputs = vtab.data_ptr()
+    return vtab
+
+
+def _compose(desc, cost_hint, tile_waves, want_current, caller_stats, pilot):
+    """Shrink-aware tile composition: an order made on the device, on the current stream, ahead of the solve.  (launch order, also set
+    in `desc`, and where its cost came from), or (None, None).  caller_stats: the `stats` tensor that `out=` carried, or None;
+    pilot: the arguments of the pilot solve.
+
+    cost_hint: where the cost comes from when compose_plan() says the launch qualifies (the lean N = 200 16-tile at one tile per
+    compute unit; 4 heaviest + 12 lightest per tile, ionode_compose_order): a 1-D fp64 / int64 device tensor [B] gives explicit
+    costs, "auto" (dopri5's default) reads the RHS evaluations of an earlier call from caller_stats (a training loop re-solves the
+    same batch with slowly changing weights) and otherwise runs a pilot first -- the HH 2-state model on the same protocols, two
+    output times, loose tolerance.  "hint" and "pilot" ask for one of the two by name; "auto" composes only the dispatcher's own
+    16-tile (tile_waves = 0), the others also a forced one.  A stale or wrong cost changes the time, never the results.
+    IONODE_COMPOSE=0|pilot|hint in the environment restricts the source."""
+    cp = compose_plan(desc, want_current)
+    if not cp["compose"]:
+        return None, None
+    B = desc.n_traj
+    # "auto" follows the dispatcher's own choice of the tile only: a forced tile_waves pins the schedule (tuning runs and tests
+    # that read per-tile effects back rely on index tiles); "pilot" / "hint" / a tensor ask for the composition explicitly
+    want = cost_hint if not (isinstance(cost_hint, str) and cost_hint == "auto" and tile_waves) else None
+    cost = composed = None
+    if isinstance(want, torch.Tensor):
+        if tuple(want.shape) != (B,):
+            raise IonodeError(f"cost_hint: expected shape {(B,)}, got {tuple(want.shape)}")
+        cost, composed = want, "explicit"
+    elif want is not None and want not in ("auto", "pilot", "hint"):
+        raise IonodeError("cost_hint: None, 'auto', 'pilot', 'hint' or a device tensor [B]")
+    elif want in ("auto", "hint") and cp["source"] in ("hint", "auto") and caller_stats is not None \
+            and _dev_ptr(caller_stats, torch.int64, "stats", (B, 4)):
+        cost, composed = caller_stats[:, 2], "hint"
+    elif want in ("auto", "pilot") and cp["source"] in ("pilot", "auto"):
+        t_eval = pilot.pop("t_eval")
+        run = dopri5(MODEL_HH2, pilot.pop("params"), pilot.pop("prot_v"), pilot.pop("y0"), torch.stack((t_eval[0], t_eval[desc.n_out - 1])),
+                     rtol=PILOT_RTOL, atol=PILOT_ATOL, t_eval_hint=None, max_total_steps=PILOT_MAX_ATTEMPTS, launch_order=None,
+                     cost_hint=None, **pilot)
+        cost, composed = run["stats"][:, 2], "pilot"
+    if cost is None:
+        return None, None
+    launch_order = compose_order(cost)
+    desc.launch_order = launch_order.data_ptr()
+    return launch_order, composed
+
+
+def _record_workspace(desc, want_current, workspace, dev):
+    """Deferred dense output: the record workspace -- the caller's (uint8, at least dense_defer_plan's bytes, 16-byte aligned: a caller
+    that wants to read the record counts back keeps it), or one from torch's caching allocator (repeat calls cost nothing) -- or None
+    when the plan defers nothing."""
+    plan = dense_defer_plan(desc, want_current)
+    if plan["capacity"] == 0:
+        return None
+    if workspace is None:
+        return torch.empty((plan["workspace_bytes"],), dtype=torch.uint8, device=dev)
+    _dev_ptr(workspace, torch.uint8, "workspace")
+    if workspace.numel() < plan["workspace_bytes"]:
+        raise IonodeError(f"workspace: {workspace.numel()} bytes, the plan asks for {plan['workspace_bytes']}")
+    return workspace
+
+
 def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, mlp_width=0, prot_t=None,
            prot_t0=0.0, prot_dt=1.0, prot_of_traj=None, rtol=1e-7, atol=1e-9, v_oob=-80.0, max_steps=0,
            max_total_steps=0, max_step=0.0, ckpt=None, current=False, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False, tile_waves=0, stats=True,
@@ -374,17 +479,8 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
     the one-trajectory-per-lane kernels when several protocols are interleaved (the 64 lanes of a wavefront then interpolate
     one protocol instead of 64: -5 % on 393 216 HH trajectories over 64 protocols).
 
-    cost_hint: where launch_order="auto" takes the cost of the shrink-aware tile composition from, when compose_plan() says the launch
-    qualifies (the lean N = 200 16-tile at one tile per compute unit; 4 heaviest + 12 lightest per tile, ionode_compose_order): a 1-D
-    fp64 / int64 device tensor [B] gives explicit costs, None composes nothing, "auto" (default) reads the RHS evaluations of an
-    earlier call from the `stats` tensor that `out=` carries (a training loop re-solves the same batch with slowly changing weights)
-    and otherwise runs a pilot first -- the HH 2-state model on the same protocols, two output times, loose tolerance.  "hint" and
-    "pilot" ask for one of the two by name; "auto" composes only the dispatcher's own 16-tile (tile_waves = 0), the others also a
-    forced one.  A stale or wrong cost changes the time, never the results.  IONODE_COMPOSE=0|pilot|hint in the environment
-    restricts the source.
-
-    workspace: optional uint8 device tensor for the deferred dense output (at least dense_defer_plan's bytes, 16-byte aligned) instead
-    of one from torch's allocator -- a caller that wants to read the record counts back (tests) keeps it.
+    cost_hint: where launch_order="auto" takes the cost of the shrink-aware tile composition from (_compose): None, "auto", "pilot",
+    "hint" or a device tensor [B].  workspace: optional uint8 device tensor for the deferred dense output (_record_workspace).
 
     params [B, n_params] f64, prot_v [P, Np] f64, y0 [B, D] f32|f64 (selects the state dtype),
     t_eval [Nt] f64.  Returns dict(y [B, Nt, D], i [B, Nt] | None, status [B] i32, stats [B, 4] i64 | None);
@@ -414,29 +510,12 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
         if mlp_packed is None or mlp_packed.dim() != 2 or mlp_packed.shape[0] * traj_per_image < B or not mlp_packed.is_contiguous():
             raise IonodeError("traj_per_image needs a contiguous mlp_packed [n_images, floats] with n_images * traj_per_image >= B")
         desc.mlp_image_stride, desc.traj_per_image = int(mlp_packed.shape[1]), int(traj_per_image)
-    # output-grid hint (t0, dt): a guess the kernel verifies against t_eval; "auto" derives it from the end points
-    # (one tiny device->host read), None disables it (cooperative scan)
-    if isinstance(t_eval_hint, str) and t_eval_hint == "auto":
-        t_eval_hint = uniform_grid(t_eval)   # pass t_eval_hint=(t0, dt) to avoid its device->host read
-        if t_eval_hint is not None and t_eval_exact is None:
-            t_eval_exact = t_eval_hint[2] == 0.0
-    if t_eval_hint is not None and t_eval_hint[1] > 0:
-        desc.t_eval_t0_hint, desc.t_eval_dt_hint = float(t_eval_hint[0]), float(t_eval_hint[1])
-        if t_eval_exact is None:
-            # exactness is a CLAIM the kernel relies on: verify it here (one tiny device->host read) unless the caller did
-            k = torch.arange(Nt, dtype=torch.float64, device=t_eval.device)
-            t_eval_exact = bool(torch.equal(t_eval, float(t_eval_hint[0]) + k * float(t_eval_hint[1])))
-        desc.t_eval_exact = int(bool(t_eval_exact))
+    _grid_hint(desc, t_eval, t_eval_hint, t_eval_exact)
     auto_order = isinstance(launch_order, str)
     if auto_order:
         if launch_order != "auto":
             raise IonodeError("launch_order: None, 'auto' or an int32 device tensor [B]")
-        launch_order = None
-        # one trajectory per lane (64 per wavefront) from these batch sizes on -- the dispatcher's crossovers (ionode_capi.hip make_plan):
-        # there the 64 lanes of a wavefront should read ONE protocol
-        lane_from = int(lib().ionode_lane_wise_from(int(model), int(mlp_width or 0)))
-        if lane_from > 0 and prot_of_traj is not None and P > 1 and B >= lane_from and not traj_per_image:
-            launch_order = _protocol_major(prot_of_traj)
+        launch_order = _auto_order(model, mlp_width, prot_of_traj, P, B, traj_per_image)
     if launch_order is not None:
         _dev_ptr(launch_order, torch.int32, "launch_order", (B,))
         desc.launch_order = launch_order.data_ptr()
@@ -449,80 +528,20 @@ def dopri5(model, params, prot_v, y0, t_eval, *, mlp_packed=None, mlp_layers=0, 
         desc.step_log = step_log.data_ptr()
         desc.step_log_cap = step_log.shape[0]
     dev = y0.device
-    if out is None:
-        out = {}
-    y = out.get("y")
-    if y is None and states:
-        y = torch.empty((B, Nt, D), dtype=sdt, device=dev)
-    sse = None
-    if sse_ref is not None:  # fused objective: [P, Nt] reference currents -> per-trajectory sum of squared residuals
-        _dev_ptr(sse_ref, torch.float64, "sse_ref", (P, Nt))
-        sse = out.get(objective)
-        if sse is None:
-            sse = torch.empty((B,), dtype=torch.float64, device=dev)
-        desc.sse_ref, desc.sse_out = sse_ref.data_ptr(), sse.data_ptr()
-    elif not states:
-        raise IonodeError("states=False needs sse_ref (something must be computed)")
-    i_out = out.get("i")
-    if current and i_out is None:
-        i_out = torch.empty((B, Nt), dtype=torch.float64, device=dev)
-    status = out.get("status")
-    if status is None:
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-    st = out.get("stats")
-    stats_from_caller = st is not None
-    if stats and st is None:
-        st = torch.empty((B, 4), dtype=torch.int64, device=dev)
+    y, sse, i_out, status, st, stats_from_caller = _outputs(out, desc, (B, Nt, D, P), sdt, dev, states, current, stats, sse_ref, objective)
     s = stream if stream is not None else torch.cuda.current_stream(dev).cuda_stream
-    # closed-form current / objective epilogue: V(t_k) once per protocol instead of once per trajectory per sample ("auto":
-    # when every protocol serves at least four trajectories; a [P, Nt] f64 tensor from an earlier call may be passed back in)
     vtab = None
     if (current or sse_ref is not None) and model in (MODEL_HH2, MODEL_MARKOV6) and v_at_outputs is not None:
-        if isinstance(v_at_outputs, str):
-            if 4 * P <= B:
-                vtab = protocol_at_outputs(desc, prot_v, prot_t, t_eval, stream=s)
-        else:
-            vtab = v_at_outputs
-            _dev_ptr(vtab, torch.float64, "v_at_outputs", (P, Nt))
-        if vtab is not None:
-            desc.v_at_outputs = vtab.data_ptr()
-    # shrink-aware tile composition: an order made on the device, on this stream, ahead of the solve.  Its buffers come from torch's
-    # caching allocator like the record workspace below, so a foreign stream composes nothing
+        vtab = _voltage_table(desc, v_at_outputs, prot_v, prot_t, t_eval, s)
+    # the composition's and the record workspace's buffers come from torch's caching allocator and go back to it when this call
+    # returns -- in stream order, which holds for torch's current stream only, so a foreign stream composes and defers nothing
     composed = None
     if auto_order and launch_order is None and cost_hint is not None and stream is None and prot_t is None and Nt >= 2:
-        cp = compose_plan(desc, i_out is not None)
-        if cp["compose"]:
-            # "auto" follows the dispatcher's own choice of the tile only: a forced tile_waves pins the schedule (tuning runs and tests
-            # that read per-tile effects back rely on index tiles); "pilot" / "hint" / a tensor ask for the composition explicitly
-            want = cost_hint if not (isinstance(cost_hint, str) and cost_hint == "auto" and tile_waves) else None
-            cost = None
-            if isinstance(want, torch.Tensor):
-                if tuple(want.shape) != (B,):
-                    raise IonodeError(f"cost_hint: expected shape {(B,)}, got {tuple(want.shape)}")
-                cost, composed = want, "explicit"
-            elif want is not None and want not in ("auto", "pilot", "hint"):
-                raise IonodeError("cost_hint: None, 'auto', 'pilot', 'hint' or a device tensor [B]")
-            elif want in ("auto", "hint") and cp["source"] in ("hint", "auto") and stats_from_caller and _dev_ptr(st, torch.int64, "stats", (B, 4)):
-                cost, composed = st[:, 2], "hint"
-            elif want in ("auto", "pilot") and cp["source"] in ("pilot", "auto"):
-                pilot = dopri5(MODEL_HH2, params, prot_v, y0, torch.stack((t_eval[0], t_eval[Nt - 1])), prot_t0=prot_t0, prot_dt=prot_dt,
-                               prot_of_traj=prot_of_traj, rtol=PILOT_RTOL, atol=PILOT_ATOL, v_oob=v_oob, t_eval_hint=None,
-                               max_total_steps=PILOT_MAX_ATTEMPTS, launch_order=None, cost_hint=None)
-                cost, composed = pilot["stats"][:, 2], "pilot"
-            if cost is not None:
-                launch_order = compose_order(cost)
-                desc.launch_order = launch_order.data_ptr()
-    # deferred dense output: the record workspace comes from torch's caching allocator (repeat calls cost nothing) and goes back to it
-    # when this call returns -- in stream order, which holds for torch's current stream only, so a foreign stream defers nothing
+        pilot = dict(params=params, prot_v=prot_v, y0=y0, t_eval=t_eval, prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=prot_of_traj, v_oob=v_oob)
+        launch_order, composed = _compose(desc, cost_hint, tile_waves, i_out is not None, st if stats_from_caller else None, pilot)
     ws = None
     if stream is None and prot_t is None and y is not None:
-        plan = dense_defer_plan(desc, i_out is not None)
-        if plan["capacity"] > 0:
-            if workspace is not None:
-                _dev_ptr(workspace, torch.uint8, "workspace")
-                if workspace.numel() < plan["workspace_bytes"]:
-                    raise IonodeError(f"workspace: {workspace.numel()} bytes, the plan asks for {plan['workspace_bytes']}")
-            ws = workspace if workspace is not None else torch.empty((plan["workspace_bytes"],), dtype=torch.uint8, device=dev)
+        ws = _record_workspace(desc, i_out is not None, workspace, dev)
     rc = lib().ionode_dopri5_objective(   # kind 0 is ionode_dopri5_composed by definition: one call site
         C.byref(desc),
         _dev_ptr(mlp_packed, torch.float32, "mlp_packed"),
@@ -562,29 +581,24 @@ def uniform_grid(t_eval):
     return (t0, dt, dev) if dt > 0 and dev <= 0.5 * dt else None
 
 
-def sweep_launch(name, desc, it_begin, it_end, n_iter, stream, **buffers):
+def sweep_launch(name, desc, it_begin, it_end, n_iter, stream, kind=None, **buffers):
     """Call the backward-sweep entry point `name` on iterations [it_begin, it_end) with its buffers BY NAME: exactly the names of
-    SWEEP_BUFFERS[name], each a device tensor or None (NULL); `stream` is a torch stream.  Raises IonodeError with the return code and
-    ionode_grad_last_error()."""
-    names = SWEEP_BUFFERS[name]
+    SWEEP_BUFFERS[name], each a device tensor or None (NULL); `stream` is a torch stream.  With `kind` (OBJECTIVE_SSE | OBJECTIVE_SAE)
+    `name` is an entry point of OBJECTIVE_BUFFERS, which takes the kind behind the descriptor.  Raises IonodeError with the return code
+    and ionode_grad_last_error()."""
+    names = (SWEEP_BUFFERS if kind is None else OBJECTIVE_BUFFERS)[name]
     if set(buffers) != set(names):
         raise TypeError(f"{name}: missing {sorted(set(names) - set(buffers))}, unknown {sorted(set(buffers) - set(names))}")
     ptrs = [None if buffers[n] is None else C.c_void_p(buffers[n].data_ptr()) for n in names]
-    rc = getattr(lib(), name)(C.byref(desc), it_begin, it_end, n_iter, *ptrs, C.c_void_p(stream.cuda_stream))
+    head = () if kind is None else (int(kind),)
+    rc = getattr(lib(), name)(C.byref(desc), *head, it_begin, it_end, n_iter, *ptrs, C.c_void_p(stream.cuda_stream))
     if rc != 0:
         raise IonodeError(f"{name} failed ({rc}): {lib().ionode_grad_last_error().decode()}")
 
 
 def objective_launch(name, desc, kind, it_begin, it_end, n_iter, stream, **buffers):
-    """sweep_launch for the entry points of OBJECTIVE_BUFFERS, which take the objective's kind (OBJECTIVE_SSE | OBJECTIVE_SAE) behind
-    the descriptor: the same named-buffer call, the same error."""
-    names = OBJECTIVE_BUFFERS[name]
-    if set(buffers) != set(names):
-        raise TypeError(f"{name}: missing {sorted(set(names) - set(buffers))}, unknown {sorted(set(buffers) - set(names))}")
-    ptrs = [None if buffers[n] is None else C.c_void_p(buffers[n].data_ptr()) for n in names]
-    rc = getattr(lib(), name)(C.byref(desc), int(kind), it_begin, it_end, n_iter, *ptrs, C.c_void_p(stream.cuda_stream))
-    if rc != 0:
-        raise IonodeError(f"{name} failed ({rc}): {lib().ionode_grad_last_error().decode()}")
+    """sweep_launch for the entry points of OBJECTIVE_BUFFERS: the same named-buffer call, the same error."""
+    sweep_launch(name, desc, it_begin, it_end, n_iter, stream, kind=int(kind), **buffers)
 
 
 def protocol_at_outputs(desc, prot_v, prot_t, t_eval, stream=None):

@@ -7,6 +7,7 @@
 #include "ionode_grad_launch.hpp"
 #include "ionode_grad_reduce.hpp"
 #include "ionode_grad_gen_plan.hpp"
+#include "ionode_host.hpp"
 
 namespace {
 
@@ -361,11 +362,7 @@ static int reduce_impl(int32_t L, int32_t N, const float *records, int64_t n_rec
 
 int32_t ionode_grad_reduce_slabs(int32_t L, int32_t N, int64_t n_records) {
   if (L < 1 || N < 1 || n_records < 1) return 1;
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
-    (void)hipGetLastError();
-    cus = 256;   // (no device: the plan of an unpartitioned MI355X)
-  }
+  const int cus = ionode::compute_units();
   const int NT = np_of(N) / 16;   // (the plan of the kernel that reduce_impl will launch for this width)
   return ionode::grad_use_gen(NT) ? ionode::grad_gen_reduce_slabs(L, NT, cus, n_records) : ionode::grad_reduce_slabs(L, NT, cus, n_records);
 }

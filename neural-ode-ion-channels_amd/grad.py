@@ -180,9 +180,7 @@ def grad_image(weights_flat, L, N, dev, key=None):
     if ck is not None and ck in _image_cache:
         return _image_cache[ck]
     w = np.ascontiguousarray(np.asarray(weights_flat, dtype=np.float32).reshape(-1))
-    expect = 2 * N + N + L * (N * N + N) + N + 1
-    if w.size != expect:
-        raise capi.IonodeError(f"state dict has {w.size} floats, (L={L}, N={N}) needs {expect}")
+    capi.state_dict_floats(w, L, N)
     n = capi.lib().ionode_grad_image_floats(L, N)
     if n == 0:
         raise capi.IonodeError("gradient path needs at least one hidden layer")
