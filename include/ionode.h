@@ -421,6 +421,31 @@ int ionode_objective_backward_gc(const ionode_desc *d, int32_t objective, int32_
                                  const double *prot_t, const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
                                  const double *grad_sse, double *packets, double *sse_grad_y0, void *stream);
 
+/*
+ * Forward sensitivities (since ABI 10, added later: new symbols only, ionode_desc and every earlier entry point unchanged).  The
+ * closed-form HH 2-state and 6-state models: the Jacobian of the current trace with respect to the rate parameters, di_k/dp_j -- PINTS
+ * ForwardModelS1.simulateS1 -- and its Gauss-Newton sums against the fused objective's reference currents.  A tangent-mode sweep over
+ * the forward launch's accepted-step checkpoints (csrc/ionode_tangent.hpp): the same discretise-then-differentiate rule as the
+ * gradients above (accepted steps are constants, rejected attempts contribute nothing, FSAL and the dense output differentiated as
+ * written), S = dy/dp zero at y0 (y0 is given), one lane per (trajectory, parameter), one launch, no chunking, no scratch state.  y_k is
+ * re-evaluated from the step's checkpoint in the state dtype (the forward's bits), tangents are fp64 whatever the state dtype, and a
+ * rate's derivative comes from the exponential the rate uses (no division by a parameter).
+ *   (NPAR = 8 for HH2, 12 for MARKOV6; all pointers DEVICE)
+ *   di_dp   [B][n_out][NPAR] fp64: di_k/dp_j, i as in the i_out epilogue; row k = 0 (y0) is zero
+ *   jtr     [B][NPAR] fp64: sum_k di_k/dp_j r_k, r_k = i_k - sse_ref[protocol][k] as in the fused objective
+ *   jtj     [B][NPAR][NPAR] fp64 (full, exactly symmetric): sum_k di_k/dp_j di_k/dp_l
+ * Each may be NULL, not all three; jtr / jtj need d->sse_ref.  The trace and the sums come from one per-sample routine and differ by
+ * summation order only (sample order per trajectory, the same bits whatever the batch).  n_accepted[b] = 0 (a failed trajectory):
+ * zero rows.  Reads model, state_f32, sizes, protocol grid, v_oob, ckpt, ckpt_cap, obs_*, sse_ref and the optional v_at_outputs from
+ * the descriptor of the forward launch that wrote the checkpoints (ionode_dopri5 with d->ckpt set).  Refusals, all before any launch,
+ * text in ionode_grad_last_error(): IONODE_ERR_ARG for a NULL descriptor, a missing required buffer (params, prot_v, t_eval,
+ * n_accepted, d->ckpt), all three outputs NULL, or sums without sse_ref; IONODE_ERR_UNSUPPORTED for NN-f / NN-d (their tangent would
+ * need a Jacobian-vector product through the MLP tiles) and for traj_per_image > 0.
+ */
+int ionode_tangent_sweep(const ionode_desc *d, const double *params, const double *prot_v, const double *prot_t,
+                         const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
+                         double *di_dp, double *jtr, double *jtj, void *stream);
+
 /* floats of one slab's partial gradient: [NP][4]{db0, dW0[.][0], dW0[.][1], 0} | L x (dW_l [NP][NP] + db_l [NP]) | dwl [NP] +
  * {dbl, 0, 0, 0}, NP = 16 * ceil(N / 16), rows/columns >= N are padding */
 size_t ionode_grad_partial_floats(int32_t mlp_layers, int32_t mlp_width);

@@ -114,6 +114,7 @@ PROTOTYPES = {
     "ionode_grad_packet_doubles": (C.c_size_t, []),
     **{name: (C.c_int, [_D] + [_I32] * 3 + [_P] * (len(buffers) + 1)) for name, buffers in SWEEP_BUFFERS.items()},
     **{name: (C.c_int, [_D] + [_I32] * 4 + [_P] * (len(buffers) + 1)) for name, buffers in OBJECTIVE_BUFFERS.items()},
+    "ionode_tangent_sweep": (C.c_int, [_D] + [_P] * 10),   # params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, di_dp, jtr, jtj, stream
     "ionode_grad_reduce": (C.c_int, _REDUCE),
     "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
     "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),

@@ -8,6 +8,7 @@
 #include "ionode_grad_reduce.hpp"
 #include "ionode_grad_gen_plan.hpp"
 #include "ionode_host.hpp"
+#include "ionode_tangent.hpp"
 
 namespace {
 
@@ -446,6 +447,38 @@ int ionode_image_refresh(int32_t L, int32_t N, const int32_t *image_map, const f
 size_t ionode_grad_partial_floats(int32_t L, int32_t N) {
   if (L < 1 || N < 1) return 0;
   return ionode::grad_partial_floats(L, np_of(N) / 16);
+}
+
+// ---- tangent (forward-mode) sweep of the closed-form models: per-sample sensitivities and their Gauss-Newton sums (ionode_tangent.hpp) ----
+// Every refusal is decided here, before the launch.
+int ionode_tangent_sweep(const ionode_desc *d, const double *params, const double *prot_v, const double *prot_t,
+                         const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
+                         double *di_dp, double *jtr, double *jtj, void *stream) {
+  constexpr const char *WHO = "ionode_tangent_sweep";
+  if (!d) return refuse(IONODE_ERR_ARG, "null descriptor");
+  if (d->model != IONODE_MODEL_HH2 && !is_m6(d)) return refuse(IONODE_ERR_UNSUPPORTED, "%s: closed-form models only (HH 2-state, 6-state)", WHO);
+  if (d->traj_per_image > 0) return refuse(IONODE_ERR_UNSUPPORTED, "%s: traj_per_image must be 0", WHO);
+  if (!desc_consistent(d)) return refuse(IONODE_ERR_ARG, "inconsistent descriptor");
+  if (!params || !prot_v || !t_eval || !n_accepted || !d->ckpt || d->ckpt_cap < 1)
+    return refuse(IONODE_ERR_ARG, "%s: required buffer is NULL (ckpt / ckpt_cap come from the descriptor)", WHO);
+  if (!di_dp && !jtr && !jtj) return refuse(IONODE_ERR_ARG, "%s: nothing to compute (di_dp, jtr and jtj are all NULL)", WHO);
+  if ((jtr || jtj) && !d->sse_ref) return refuse(IONODE_ERR_ARG, "%s: jtr / jtj need the reference currents (sse_ref comes from the descriptor)", WHO);
+
+  ionode::TArgs t;
+  memset(&t, 0, sizeof t);
+  GArgs &a = t.g;
+  a.k.params = params; a.k.prot_v = prot_v; a.k.prot_t = prot_t; a.k.prot_of_traj = prot_of_traj; a.k.t_eval = t_eval;
+  a.k.B = d->n_traj; a.k.Nt = d->n_out; a.k.P = d->n_prot; a.k.Np = d->prot_n; a.k.n_params = d->n_params;
+  a.k.NP = 16; a.k.NT = 1;
+  a.k.prot_t0 = d->prot_t0; a.k.prot_dt = d->prot_dt; a.k.prot_rdt = 1.0 / d->prot_dt; a.k.v_oob = d->v_oob;
+  a.ckpt = d->ckpt; a.ckpt_cap = d->ckpt_cap; a.nacc = n_accepted;
+  a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
+  a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
+  t.di_dp = di_dp; t.jtr = jtr; t.jtj = jtj;
+  ionode::launch_tangent(d->model, d->state_f32 ? 1 : 0, t, reinterpret_cast<hipStream_t>(stream));
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return refuse(IONODE_ERR_LAUNCH, "%s", hipGetErrorString(err));
+  return IONODE_OK;
 }
 
 }  // extern "C"

@@ -104,6 +104,7 @@ def _forward_with_checkpoints(ctx, weights_flat, params, y0, cfg, objective):
     if objective:
         kw.update(obs_g=cfg["obs_g"], obs_e=cfg["obs_e"], obs_open_state_only=cfg["obs_open_state_only"], sse_ref=cfg["sse_ref"], states=False,
                   objective=cfg["objective"])
+    kw.update(cfg.get("forward_kw") or {})   # (sensitivity.current_s1: the current epilogue beside the states)
     cap = int(cfg.get("ckpt_cap") or DEFAULT_CKPT_CAP)
     limit = _bounded_budget(cfg.get("ckpt_budget_bytes"), DEFAULT_CKPT_BUDGET, dev, 0.6)
     row_bytes = B * capi.ckpt_record_doubles(D) * 8

@@ -236,3 +236,82 @@ def _population_error_s1(kind, candidates, protocols_v, data_i, t_eval, *, base_
         dist.all_gather(parts, pad, group=group)
         out = torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
     return out[:, 0].contiguous(), out[:, 1:].contiguous()
+
+
+def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=False, prot_t0=0.0,
+                            prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False,
+                            max_total_steps=1_000_000, max_step="auto", group=None, device=None, solver=None, cost=None,
+                            model=capi.MODEL_HH2):
+    """Sum-of-squares error of every candidate with its gradient AND its Gauss-Newton Hessian in the free parameters: what a
+    Gauss-Newton / Levenberg-Marquardt step or a Fisher-information estimate needs, from forward sensitivities
+    (sensitivity.gauss_newton: PINTS ForwardModelS1.simulateS1 contracted in the kernel, no trace of size [C * P, Nt] is written).
+
+    Arguments, models, sharding, the population-wide "auto" step cap and the all-gather as population_sum_of_squares_s1.  Returns
+    (sse [C], g [C, len(free)], H [C, len(free), len(free)]) fp64 on the device, summed over the candidate's protocols: with the
+    residuals r and the Jacobian J = dr/d(free parameters), g = 2 J^T r -- population_sum_of_squares_s1's gradient by another route --
+    and H = 2 J^T J.  log_parameters=True: derivatives with respect to log p_j (the reference's pints.LogTransformation,
+    train-d0.py:511), g_j p_j and H_jl p_j p_l.  A candidate any of whose solves failed gets sse = inf and ZERO g and H.
+    `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature, so the sharding / all-gather logic can run without a
+    GPU.  No optimiser here: the damping, the step and its acceptance are the caller's; no y0 sensitivities, no NN models, no
+    absolute-error variant (sensitivity's module docstring).
+    """
+    who = "population_gauss_newton"
+    import torch.distributed as dist
+    from . import sensitivity
+    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
+        raise capi.IonodeError(f"{who}: HH 2-state and 6-state models only")
+    D, npar = (6, 12) if model == capi.MODEL_MARKOV6 else (2, 8)
+    free = [int(f) for f in free]
+    cand = np.asarray(candidates, dtype=np.float64).reshape(-1, len(free))
+    C, P = cand.shape[0], np.asarray(protocols_v).shape[0]
+    base = np.asarray(base_params, dtype=np.float64)
+    if base.shape != (npar,) or len(y0) != D:
+        raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
+    on = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+    if cost is not None and len(cost) != C:
+        raise capi.IonodeError(f"cost has {len(cost)} entries for {C} candidates: the shards would not cover the population")
+    bounds = [distributed.shard_bounds(C, r, world) for r in range(world)] if cost is None \
+        else distributed.shard_bounds_by_cost(cost, world)
+    lo, hi = bounds[rank]
+    dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
+    solve = sensitivity.gauss_newton if solver is None else solver
+    params_all = np.tile(base, (C, 1))
+    params_all[:, free] = cand
+    if isinstance(max_step, str):
+        if max_step != "auto":
+            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
+        fin = np.isfinite(params_all).all(axis=1)   # (a non-finite candidate fails either way; it must not void everyone's cap)
+        max_step = grad.stable_step_cap(model, torch.from_numpy(params_all[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
+            if fin.any() else 0.0
+    nf = len(free)
+    out = torch.empty((hi - lo, 1 + nf + nf * nf), dtype=torch.float64, device=dev)
+    if hi > lo:
+        n = hi - lo
+        p = torch.from_numpy(np.repeat(params_all[lo:hi], P, axis=0)).to(dev)   # trajectory = c * P + protocol
+        pot = torch.from_numpy(np.tile(np.arange(P, dtype=np.int32), n)).to(dev)
+        y0t = torch.tensor([list(y0)], dtype=state_dtype, device=dev).expand(n * P, D).contiguous()
+        sse, jtr, jtj, status = solve(model, p, torch.as_tensor(np.asarray(protocols_v), dtype=torch.float64, device=dev).contiguous(), y0t,
+                                      torch.as_tensor(np.asarray(t_eval), dtype=torch.float64, device=dev).contiguous(),
+                                      torch.as_tensor(np.asarray(data_i), dtype=torch.float64, device=dev).contiguous(),
+                                      prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=pot, obs_g=obs_g, obs_e=obs_e,
+                                      obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=max_step)
+        ok = (status.reshape(n, P) == 0).all(dim=1)
+        err = sse.reshape(n, P).sum(dim=1)
+        g = 2.0 * jtr.reshape(n, P, npar).sum(dim=1)[:, free]
+        H = 2.0 * jtj.reshape(n, P, npar, npar).sum(dim=1)[:, free][:, :, free]
+        if log_parameters:   # d/d log p_j = p_j d/dp_j
+            pf = torch.from_numpy(params_all[lo:hi][:, free]).to(dev)
+            g, H = g * pf, H * pf[:, :, None] * pf[:, None, :]
+        out[:, 0] = torch.where(ok, err, torch.full_like(err, float("inf")))
+        out[:, 1:1 + nf] = torch.where(ok[:, None], g, torch.zeros_like(g))
+        out[:, 1 + nf:] = torch.where(ok[:, None], H.reshape(n, nf * nf), torch.zeros((), dtype=torch.float64, device=dev))
+    if world > 1:
+        m = max(b[1] - b[0] for b in bounds)
+        pad = torch.zeros((m, out.shape[1]), dtype=torch.float64, device=dev)
+        pad[:, 0] = float("inf")
+        pad[: hi - lo] = out
+        parts = [torch.empty_like(pad) for _ in range(world)]
+        dist.all_gather(parts, pad, group=group)
+        out = torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
+    return out[:, 0].contiguous(), out[:, 1:1 + nf].contiguous(), out[:, 1 + nf:].reshape(-1, nf, nf).contiguous()
