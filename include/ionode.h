@@ -504,6 +504,89 @@ int ionode_image_refresh(int32_t mlp_layers, int32_t mlp_width, const int32_t *i
 
 const char *ionode_grad_last_error(void);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Levenberg-Marquardt step for a population of candidates (closed-form models; new symbols, ABI stays 10).
+ * A fit is a loop of two launches on one stream with no host synchronisation between them: the Gauss-Newton evaluation
+ * (the checkpointed forward with the fused objective, then the tangent sweep's jtr / jtj) of the trial tensor, then the step
+ * entry point below on its outputs, which decides about the trial points and writes the next trial tensor in place.
+ *
+ * Candidate c has nf free parameters x (columns free_idx[] of its NPAR rate parameters; the others are base[]) and the search
+ * variables u = log x (log_parameters) or u = x.  Launch slot s holds candidate active[s] (active == NULL: candidate s): the
+ * evaluation arrays and the trial tensor are indexed by slot -- the slot's P trajectories are rows s * P .. s * P + P - 1, one per
+ * protocol -- and state / flag / iters by candidate.
+ *
+ * One call, for every slot whose candidate is running (flag 0):
+ *   reduce   f_t = sum_p sse, g_t = 2 sum_p jtr[free], H_t = 2 sum_p jtj[free][free], each over p = 0 .. P - 1 in that order; a
+ *            non-zero status on any of the P trajectories makes f_t = +inf.  log_parameters: g_j x_j and H_jl (x_j x_l).  Only the
+ *            lower triangle of jtj is read; H is stored with its mirror and is exactly symmetric.
+ *   decide   rho = (f - f_t) / pred, pred as the previous call stored it.  Accepted when f_t < f and rho > rho_accept: (u, x, f,
+ *            g, H) <- trial, lam <- lam max(1/3, 1 - (2 rho - 1)^3), nu <- 2.  Otherwise lam <- lam nu, nu <- 2 nu (Nielsen's rule).
+ *            A state with f = +inf -- the first call of a fit -- accepts any finite evaluation and leaves lam and nu alone.
+ *   stop     IONODE_LM_FTOL: accepted with f - f_t <= ftol f;  IONODE_LM_GTOL: accepted and max_j |g_j| <= gtol over the variables
+ *            that are not held (below);
+ *            IONODE_LM_STALLED: lam > lam_max (after a rejection, or after the retries below);  IONODE_LM_XTOL: the projected step
+ *            d has |d|_2 <= xtol (|u|_2 + xtol);  IONODE_LM_MAXITER: evaluations >= max_iter;  IONODE_LM_NONFINITE: the first
+ *            evaluation is not finite (a non-finite start), or an accepted evaluation has a non-finite g or H.  Where several
+ *            hold, the first of FTOL / NONFINITE, GTOL, STALLED, XTOL, MAXITER is stored.  A candidate whose flag is not 0 is frozen:
+ *            a later call changes nothing of its state, flag or iters and writes its accepted x into its slot's trial rows.
+ *   propose  (H + lam D) delta = -g by Cholesky, D_j = max(H_jj, IONODE_LM_FLOOR_REL max_l H_ll, IONODE_LM_FLOOR_ABS): Marquardt's
+ *            diagonal scaling with a floor that keeps D positive for every finite H.  A pivot that is not a positive finite number,
+ *            or a non-finite delta, sets lam <- lam nu, nu <- 2 nu and factors again, at most IONODE_LM_RETRIES times; then the
+ *            candidate is IONODE_LM_STALLED.  A variable at a bound whose gradient points out of the box (u_j <= lo_j and g_j > 0,
+ *            or u_j >= hi_j and g_j < 0) is held: delta_j = 0 and its row and column leave the system.  Trial point ut = min(max(u + delta, lo), hi) in the search space, d = ut - u,
+ *            xt = exp(ut) clamped into [lo, hi] (log_parameters; the library's deterministic exp) or xt = ut, and
+ *            pred = -(g . d + d . H d / 2).  The slot's P trial rows are base[] with the free columns replaced by xt.
+ *
+ * state [n_cand][IONODE_LM_STATE_U + 6 nf + nf^2] fp64, per candidate:
+ *   [IONODE_LM_STATE_F] f, [IONODE_LM_STATE_LAM] lam, [IONODE_LM_STATE_NU] nu, [IONODE_LM_STATE_PRED] pred, then from
+ *   IONODE_LM_STATE_U on: u[nf], x[nf], g[nf], ut[nf], xt[nf], delta[nf] (the last solution of the damped system, before the
+ *   projection), H[nf][nf].
+ * To start a fit the caller sets f = +inf, lam = its initial damping, nu = 2, pred = 0, u = ut = the start in the search space,
+ * x = xt = the start, the rest 0, flag = 0, iters = 0, and writes the starts into the trial tensor.
+ *
+ * The host entry point is the same per-candidate routine compiled for the host, on host pointers, no HIP call: its results equal
+ * the kernel's bit for bit.  Results of a candidate do not depend on the other candidates of the call.
+ * Refusals, all before any launch, text in ionode_grad_last_error(): IONODE_ERR_ARG for a NULL descriptor or buffer (active may
+ * be NULL), n_free outside 1 .. IONODE_LM_MAX_FREE, n_params not 8 or 12, a free index outside n_params, lo > hi (or a NaN
+ * bound), non-positive bounds with log_parameters, or n_cand / n_active / n_prot / max_iter < 1 or n_active > n_cand.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define IONODE_LM_MAX_FREE 12
+#define IONODE_LM_RETRIES 8            /* factorisations after the first that one call may try */
+#define IONODE_LM_FLOOR_REL 0x1p-20    /* D_j >= this times the largest diagonal entry of H */
+#define IONODE_LM_FLOOR_ABS 0x1p-256   /* D_j >= this, whatever H */
+#define IONODE_LM_STATE_F 0
+#define IONODE_LM_STATE_LAM 1
+#define IONODE_LM_STATE_NU 2
+#define IONODE_LM_STATE_PRED 3
+#define IONODE_LM_STATE_U 4
+#define IONODE_LM_RUNNING 0
+#define IONODE_LM_GTOL 1
+#define IONODE_LM_XTOL 2
+#define IONODE_LM_FTOL 3
+#define IONODE_LM_STALLED 4
+#define IONODE_LM_MAXITER 5
+#define IONODE_LM_NONFINITE 6
+
+typedef struct ionode_lm_desc {
+  int32_t n_cand;          /* candidates the state arrays hold */
+  int32_t n_active;        /* launch slots of this call, <= n_cand */
+  int32_t n_prot;          /* P: trajectories per candidate */
+  int32_t n_params;        /* NPAR: 8 (HH 2-state) or 12 (6-state) */
+  int32_t n_free;          /* nf */
+  int32_t log_parameters;
+  int32_t max_iter;        /* evaluations a candidate may use */
+  int32_t reserved;
+  int32_t free_idx[IONODE_LM_MAX_FREE];
+  double base[IONODE_LM_MAX_FREE];
+  double lo[IONODE_LM_MAX_FREE], hi[IONODE_LM_MAX_FREE];   /* the box, in the parameters; -inf / +inf: none (log_parameters: lo > 0, DBL_MIN for none) */
+  double gtol, xtol, ftol, rho_accept, lam_max;
+} ionode_lm_desc;
+
+int ionode_lm_step(const ionode_lm_desc *d, const int32_t *active, const double *sse, const double *jtr, const double *jtj,
+                   const int32_t *status, double *state, int32_t *flag, int32_t *iters, double *trial, void *stream);
+int ionode_lm_step_host(const ionode_lm_desc *d, const int32_t *active, const double *sse, const double *jtr, const double *jtj,
+                        const int32_t *status, double *state, int32_t *flag, int32_t *iters, double *trial);
+
 #ifdef __cplusplus
 }
 #endif

@@ -82,6 +82,40 @@ class IonodeError(RuntimeError):
     pass
 
 
+# the Levenberg-Marquardt step (include/ionode.h ionode_lm_desc, IONODE_LM_*): descriptor, state layout, stop flags
+LM_MAX_FREE, LM_RETRIES, LM_FLOOR_REL, LM_FLOOR_ABS = 12, 8, 2.0 ** -20, 2.0 ** -256
+LM_STATE_F, LM_STATE_LAM, LM_STATE_NU, LM_STATE_PRED, LM_STATE_U = 0, 1, 2, 3, 4
+LM_RUNNING, LM_GTOL, LM_XTOL, LM_FTOL, LM_STALLED, LM_MAXITER, LM_NONFINITE = range(7)
+LM_FLAG_TEXT = {0: "running", 1: "gradient below gtol", 2: "step below xtol", 3: "reduction below ftol", 4: "stalled (damping above lam_max)",
+                5: "iteration cap", 6: "non-finite start or derivative"}
+
+
+class IonodeLmDesc(C.Structure):
+    _fields_ = [
+        ("n_cand", C.c_int32), ("n_active", C.c_int32), ("n_prot", C.c_int32), ("n_params", C.c_int32),
+        ("n_free", C.c_int32), ("log_parameters", C.c_int32), ("max_iter", C.c_int32), ("reserved", C.c_int32),
+        ("free_idx", C.c_int32 * LM_MAX_FREE), ("base", C.c_double * LM_MAX_FREE),
+        ("lo", C.c_double * LM_MAX_FREE), ("hi", C.c_double * LM_MAX_FREE),
+        ("gtol", C.c_double), ("xtol", C.c_double), ("ftol", C.c_double), ("rho_accept", C.c_double), ("lam_max", C.c_double),
+    ]
+
+
+def lm_state_doubles(nf):
+    """fp64 words of one candidate's Levenberg-Marquardt state: f, lam, nu, pred, then u, x, g, ut, xt, delta [nf] and H [nf][nf]."""
+    return LM_STATE_U + 6 * nf + nf * nf
+
+
+def lm_state_views(state, nf):
+    """Named views of a state array [C, lm_state_doubles(nf)] (numpy or torch): f, lam, nu, pred [C]; u, x, g, ut, xt, delta [C, nf];
+    H [C, nf, nf]."""
+    o = LM_STATE_U
+    v = {"f": state[:, LM_STATE_F], "lam": state[:, LM_STATE_LAM], "nu": state[:, LM_STATE_NU], "pred": state[:, LM_STATE_PRED]}
+    for k, name in enumerate(("u", "x", "g", "ut", "xt", "delta")):
+        v[name] = state[:, o + k * nf:o + (k + 1) * nf]
+    v["H"] = state[:, o + 6 * nf:o + 6 * nf + nf * nf].reshape(state.shape[0], nf, nf)
+    return v
+
+
 # Every symbol of include/ionode.h: name -> (restype, argtypes); lib() applies the table, EXPORTS is its keys.
 _D, _P, _I32, _I64, _F32 = C.POINTER(IonodeDesc), C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _SOLVE = [_D] + [_P] * 12   # ionode_dopri5: d, mlp_packed .. stats, stream -- the solve family's common prefix
@@ -115,6 +149,9 @@ PROTOTYPES = {
     **{name: (C.c_int, [_D] + [_I32] * 3 + [_P] * (len(buffers) + 1)) for name, buffers in SWEEP_BUFFERS.items()},
     **{name: (C.c_int, [_D] + [_I32] * 4 + [_P] * (len(buffers) + 1)) for name, buffers in OBJECTIVE_BUFFERS.items()},
     "ionode_tangent_sweep": (C.c_int, [_D] + [_P] * 10),   # params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, di_dp, jtr, jtj, stream
+    # d, active, sse, jtr, jtj, status, state, flag, iters, trial (, stream)
+    "ionode_lm_step": (C.c_int, [C.POINTER(IonodeLmDesc)] + [_P] * 10),
+    "ionode_lm_step_host": (C.c_int, [C.POINTER(IonodeLmDesc)] + [_P] * 9),
     "ionode_grad_reduce": (C.c_int, _REDUCE),
     "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
     "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),

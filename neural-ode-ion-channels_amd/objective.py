@@ -252,8 +252,9 @@ def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_par
     and H = 2 J^T J.  log_parameters=True: derivatives with respect to log p_j (the reference's pints.LogTransformation,
     train-d0.py:511), g_j p_j and H_jl p_j p_l.  A candidate any of whose solves failed gets sse = inf and ZERO g and H.
     `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature, so the sharding / all-gather logic can run without a
-    GPU.  No optimiser here: the damping, the step and its acceptance are the caller's; no y0 sensitivities, no NN models, no
-    absolute-error variant (sensitivity's module docstring).
+    GPU.  The optimiser built on these sums is population_fit (fit.py: Levenberg-Marquardt with the reduction, the damping, the
+    step and its acceptance in one kernel); no y0 sensitivities, no NN models, no absolute-error variant (sensitivity's module
+    docstring).
     """
     who = "population_gauss_newton"
     import torch.distributed as dist
@@ -315,3 +316,76 @@ def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_par
         dist.all_gather(parts, pad, group=group)
         out = torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
     return out[:, 0].contiguous(), out[:, 1:1 + nf].contiguous(), out[:, 1 + nf:].reshape(-1, nf, nf).contiguous()
+
+
+def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds=None, prot_t0=0.0,
+                   prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False,
+                   max_total_steps=1_000_000, max_step="auto", rtol=1e-7, atol=1e-9, group=None, device=None, solver=None, cost=None,
+                   model=capi.MODEL_HH2, max_iter=50, gtol=1e-8, xtol=1e-8, ftol=1e-8, lam_init=1e-3, compact_every=4):
+    """Multi-start Levenberg-Marquardt: every candidate is the start of a fit of the free parameters to data_i, all of them iterated
+    together (fit.levenberg_marquardt: one sensitivity.gauss_newton evaluation and one ionode_lm_step launch per iteration, one read
+    of the stop flags every compact_every iterations).
+
+    candidates [C, len(free)] starting points; the other arguments as population_gauss_newton, plus bounds = (lo, hi) in the
+    parameters (None: unbounded), the solve's rtol / atol, and the stopping rule (max_iter evaluations per candidate, gtol, xtol, ftol,
+    lam_init: include/ionode.h "Levenberg-Marquardt step").  log_parameters (default, the reference's pints.LogTransformation,
+    train-d0.py:511): the search runs in log p.  Returns (x [C, len(free)], sse [C], flag [C] int32, iterations [C, 2] int32 =
+    (evaluations, accepted)) on the device: the best accepted point of every start, its sum of squares (inf where the start could not
+    be evaluated), why it stopped (capi.LM_*: never 0) and what it cost.
+    max_step "auto" is resolved ONCE, before the loop and before sharding: grad.stable_step_cap at the upper corner of the box --
+    the stiffest point the fit can visit -- or, without bounds, over the starting population; the cap is then held, so the function
+    being minimised is the same in every iteration and on every rank.
+    Sharding as population_sum_of_squares_s1 (contiguous, or equal cost with `cost`); the fits of a shard need nothing from the
+    others, so there is no communication during the fit and one all-gather of [C, len(free) + 4] at its end.  A candidate's result
+    does not depend on the shard it ran in.  `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature on CPU
+    tensors -- the step then runs as ionode_lm_step_host and the loop, the compaction and the all-gather need no GPU.
+    Out of scope: the NN models (their tangent sweep is refused), CMA-ES, a noise model, sensitivities with respect to y0.
+    """
+    who = "population_fit"
+    import torch.distributed as dist
+    from . import fit
+    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
+        raise capi.IonodeError(f"{who}: HH 2-state and 6-state models only")
+    D, npar = (6, 12) if model == capi.MODEL_MARKOV6 else (2, 8)
+    free = [int(f) for f in free]
+    nf = len(free)
+    cand = np.asarray(candidates, dtype=np.float64).reshape(-1, nf)
+    C = cand.shape[0]
+    base = np.asarray(base_params, dtype=np.float64)
+    if base.shape != (npar,) or len(y0) != D:
+        raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
+    on = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+    if cost is not None and len(cost) != C:
+        raise capi.IonodeError(f"cost has {len(cost)} entries for {C} candidates: the shards would not cover the population")
+    bounds_r = [distributed.shard_bounds(C, r, world) for r in range(world)] if cost is None \
+        else distributed.shard_bounds_by_cost(cost, world)
+    lo, hi = bounds_r[rank]
+    dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
+    if isinstance(max_step, str):
+        if max_step != "auto":
+            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
+        corner = np.tile(base, (C, 1))
+        if bounds is not None and np.isfinite(np.asarray(bounds[1], dtype=np.float64)).all():
+            corner = corner[:1]
+            corner[:, free] = np.asarray(bounds[1], dtype=np.float64)
+        else:
+            corner[:, free] = cand
+        fin = np.isfinite(corner).all(axis=1)   # (a non-finite start fails either way; it must not void everyone's cap)
+        max_step = grad.stable_step_cap(model, torch.from_numpy(corner[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
+            if fin.any() else 0.0
+    x, sse, flag, iters = fit.levenberg_marquardt(model, cand[lo:hi], protocols_v, data_i, t_eval, base_params=base, free=free,
+                                                  log_parameters=log_parameters, bounds=bounds, prot_t0=prot_t0, prot_dt=prot_dt, y0=y0,
+                                                  state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e, obs_open_state_only=obs_open_state_only,
+                                                  max_total_steps=max_total_steps, max_step=float(max_step), rtol=rtol, atol=atol, device=dev,
+                                                  solver=solver, max_iter=max_iter, gtol=gtol, xtol=xtol, ftol=ftol, lam_init=lam_init,
+                                                  compact_every=compact_every)
+    out = torch.cat([x, sse[:, None], flag.double()[:, None], iters.double()], dim=1)   # [n, nf + 4]
+    if world > 1:
+        m = max(b[1] - b[0] for b in bounds_r)
+        pad = torch.zeros((m, nf + 4), dtype=torch.float64, device=dev)
+        pad[: hi - lo] = out
+        parts = [torch.empty_like(pad) for _ in range(world)]
+        dist.all_gather(parts, pad, group=group)
+        out = torch.cat([parts[r][: bounds_r[r][1] - bounds_r[r][0]] for r in range(world)])
+    return out[:, :nf].contiguous(), out[:, nf].contiguous(), out[:, nf + 1].to(torch.int32), out[:, nf + 2:].to(torch.int32).contiguous()

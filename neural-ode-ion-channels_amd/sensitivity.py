@@ -11,7 +11,7 @@ csrc/ionode_tangent.hpp) -- the same rule as grad.py's reverse mode, so 2 J^T r 
 Two launches: the checkpointed forward (capi.dopri5, sized and regrown by grad._forward_with_checkpoints) and ionode_tangent_sweep.
 Plain evaluations: no autograd graph is built, and there is no CPU fallback.
 
-Out of scope: an optimiser (a Levenberg-Marquardt driver builds on gauss_newton), sensitivities with respect to y0, the NN models
+The optimiser is not here: fit.py's Levenberg-Marquardt driver builds on gauss_newton.  Out of scope: sensitivities with respect to y0, the NN models
 (their tangent needs a Jacobian-vector product through the MLP tiles) and an absolute-error variant of the sums.
 """
 import ctypes as C
@@ -115,7 +115,7 @@ def gauss_newton(model, params, prot_v, y0, t_eval, sse_ref, *, prot_t=None, pro
     (full, exactly symmetric).  The gradient of sse is 2 jtr, its Gauss-Newton Hessian 2 jtj.  Failed trajectories: zero jtr, jtj.
     The sums and current_s1's trace come from one per-sample device routine and differ by summation order only.
     The output grid must be uniform (the fused forward's output cursor, the rule of grad.sum_of_squares); for any other t_eval use
-    sensitivity.current_s1 and contract the trace in torch.  No optimiser: a Levenberg-Marquardt driver is the caller's."""
+    sensitivity.current_s1 and contract the trace in torch.  The Levenberg-Marquardt driver on these sums: fit.levenberg_marquardt."""
     kw = dict(prot_t=prot_t, prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=prot_of_traj, obs_g=obs_g, obs_e=obs_e,
               obs_open_state_only=obs_open_state_only, rtol=rtol, atol=atol, v_oob=v_oob, max_steps=max_steps, max_total_steps=max_total_steps,
               max_step=max_step, ckpt_cap=ckpt_cap, ckpt_budget_bytes=ckpt_budget_bytes)
