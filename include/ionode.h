@@ -587,6 +587,122 @@ int ionode_lm_step(const ionode_lm_desc *d, const int32_t *active, const double 
 int ionode_lm_step_host(const ionode_lm_desc *d, const int32_t *active, const double *sse, const double *jtr, const double *jtj,
                         const int32_t *status, double *state, int32_t *flag, int32_t *iters, double *trial);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * CMA-ES step for many independent runs (all four models, either objective kind; new symbols, ABI stays 10).
+ * The reference fits its candidate models with PINTS' CMA-ES (train-d0.py:508-540).  Here K runs -- restarts, cells, start
+ * points, seeds -- advance together, each with lambda candidates per generation and P protocols per candidate.  A generation
+ * of all runs is two launches on one stream with no host synchronisation between them: the forward solve with the fused
+ * objective (either kind) on the trial tensor [n_active * lambda * P][NPAR], then the step entry point below on its
+ * per-trajectory values and statuses: the TELL of the generation just evaluated, then the ASK of the next, which overwrites
+ * the trial tensor in place.  A run whose generation counter iters[run][0] is 0 skips the tell: the first call only samples.
+ *
+ * Launch slot s holds run active[s] (active == NULL: run s).  value / status / trial are indexed by slot -- candidate k of the
+ * slot owns rows (s lambda + k) P .. + P - 1, one per protocol -- and state / flag / iters by run.
+ *
+ * The algorithm is Hansen's (mu/mu_w, lambda)-CMA-ES ("The CMA Evolution Strategy: A Tutorial", arXiv 1604.00772) with positive
+ * weights only, in n = n_free search variables u = log x (log_parameters) or u = x:
+ *   mu = floor(lambda / 2), w_i = (ln(mu + 1/2) - ln i) / sum, i = 1 .. mu, mu_eff = 1 / sum w_i^2,
+ *   c_sigma = (mu_eff + 2) / (n + mu_eff + 5), d_sigma = 1 + 2 max(0, sqrt((mu_eff - 1) / (n + 1)) - 1) + c_sigma,
+ *   c_c = (4 + mu_eff / n) / (n + 4 + 2 mu_eff / n), c_1 = 2 / ((n + 1.3)^2 + mu_eff),
+ *   c_mu = min(1 - c_1, 2 (mu_eff - 2 + 1 / mu_eff) / ((n + 2)^2 + mu_eff)), chi_n = sqrt(n) (1 - 1 / (4 n) + 1 / (21 n^2)).
+ *   (The default lambda, 4 + floor(3 ln n), is the caller's to set: lambda arrives in the descriptor, 2 .. IONODE_CMAES_MAX_LAMBDA.)
+ *   tell   f_k = sum_p value, p = 0 .. P - 1 in that order; a non-zero status on any of the P rows, or a NaN, makes f_k = +inf.
+ *          Rank by (f, k).  The best-ever (f, x) of the run is updated.  Fewer than mu finite values: IONODE_CMAES_NONFINITE and
+ *          nothing else of the state moves.  Otherwise, with y_k = (u_k - m) / sigma of the points AS EVALUATED (after redraws
+ *          and clipping) and y_w = sum w_rank(k) y_k:  m <- m + sigma y_w;  p_sigma <- (1 - c_sigma) p_sigma + sqrt(c_sigma (2 -
+ *          c_sigma) mu_eff) B D^-1 B^T y_w;  sigma <- sigma exp(min(1, (c_sigma / d_sigma) (|p_sigma| / chi_n - 1)));
+ *          h_sigma = |p_sigma| / sqrt(1 - (1 - c_sigma)^(2 g)) / chi_n < 1.4 + 2 / (n + 1), g the number of tells so far;
+ *          p_c <- (1 - c_c) p_c + h_sigma sqrt(c_c (2 - c_c) mu_eff) y_w;  C <- (1 - c_1 - c_mu + (1 - h_sigma) c_1 c_c (2 - c_c)) C
+ *          + c_1 p_c p_c^T + c_mu sum w_rank(k) y_k y_k^T, symmetrised first and written as a symmetric pair;  then C = B D^2 B^T
+ *          by cyclic Jacobi, every generation: row-cyclic sweeps over (p, q), p < q, a rotation wherever |a_pq| > 2^-54
+ *          sqrt(|a_pp a_qq|), until a sweep rotates nothing or IONODE_CMAES_JACOBI_SWEEPS sweeps are done.  D_j = sqrt(max(eigenvalue, 0)),
+ *          in the order the diagonal leaves them (not sorted).
+ *   stop   the first that holds of IONODE_CMAES_NONFINITE (above, or a non-finite sigma or D), IONODE_CMAES_UNCHANGED (the best
+ *          f did not fall by more than unchanged_threshold below the last significant best for unchanged_iters tells: PINTS' rule),
+ *          IONODE_CMAES_TOLX (sigma max_j max(sqrt(C_jj), |p_c,j|) < tolx), IONODE_CMAES_CONDITION (max D / min D >
+ *          IONODE_CMAES_CONDITION_LIMIT), IONODE_CMAES_MAXITER (tells >= max_iter).  A run whose flag is not 0 is frozen: a later
+ *          call changes nothing of its state, flag or iters and writes its best x into all of its slot's trial rows.
+ *   ask    candidate k, generation g: z from the generator below, u_k = m + sigma B (D z).  A point outside the box is
+ *          redrawn whole with the next attempt index, IONODE_CMAES_RESAMPLES times at most, then clipped into the box.
+ *          x_k = exp(u_k) clamped into [lo, hi] (log_parameters; the library's deterministic exp) or x_k = u_k.  u_k and x_k are
+ *          kept in the state; the candidate's P trial rows are base[] with the free columns replaced by x_k.
+ *
+ * Random numbers: Philox4x32-10 (Salmon et al. 2011), counter (run_base + run, generation, candidate, pair + 65536 attempt), key (low, high
+ * word of seed); words 0, 1 and 2, 3 give two uniforms ((w_hi 2^21 + (w_lo >> 11)) + 1/2) 2^-53 and Wichura's AS241 PPND16 turns
+ * each into a normal deviate: coordinates 2 pair and 2 pair + 1.  Its logarithm is the library's own operation sequence (exponent
+ * by bit extraction, mantissa in [sqrt(1/2), sqrt(2)], the atanh series in s = (m - 1) / (m + 1) to s^23): a draw is a pure
+ * function of its indices, the same on the host and on the device, whoever shares the launch.
+ *
+ * state [n_run][IONODE_CMAES_STATE_M + 8 n + 3 n^2 + 2 lambda + 2 lambda n] fp64, per run: the scalars IONODE_CMAES_STATE_SIGMA ..
+ * _COND (sigma, sigma before the last tell, best f, the last significant best f, tells since then, h_sigma, finite values of the
+ * last tell, the flag, the last rotation's c and s, the rotations of the last sweep, max D / min D), then from IONODE_CMAES_STATE_M
+ * on: m, m before the last tell, p_c, p_sigma, D, best x, y_w, D^-1 B^T y_w [n each]; C, B, the Jacobi work matrix [n][n each,
+ * row-major]; f, the weight each candidate's rank earned [lambda each]; the points u [lambda][n] and x [lambda][n].
+ * To start a fit the caller sets sigma = sigma0, best f = last significant best = +inf, m = the start in the search space,
+ * best x = the start, D_j = s_j, C = diag(s_j^2), B = I, the rest 0, flag = 0, iters = 0.  iters [n_run][2]: generations sampled,
+ * evaluations told.
+ *
+ * Execution model: one 64-lane workgroup per run, the run's state staged in LDS, the step a sequence of phases with a workgroup
+ * barrier between them; in a phase a lane writes only elements it owns and every sum is one lane's, in one written order.  The
+ * host entry point runs the same phase functions, lane after lane, phase after phase, on host pointers, no HIP call: its results
+ * equal the kernel's bit for bit, and a run's results do not depend on the other runs of the call.
+ * Refusals, all before anything is touched, text in the gradient path's error string: IONODE_ERR_ARG for a NULL descriptor
+ * or buffer (active may be NULL), n_free outside 1 .. IONODE_LM_MAX_FREE, lambda outside 2 .. IONODE_CMAES_MAX_LAMBDA, n_params outside
+ * 1 .. IONODE_LM_MAX_FREE, a free index outside n_params, lo > hi (or a NaN bound), non-positive bounds with log_parameters, or
+ * n_run / n_active / n_prot / max_iter / unchanged_iters < 1 or n_active > n_run.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define IONODE_CMAES_MAX_LAMBDA 64
+#define IONODE_CMAES_RESAMPLES 8          /* redraws of a point outside the box before it is clipped */
+#define IONODE_CMAES_JACOBI_SWEEPS 30
+#define IONODE_CMAES_CONDITION_LIMIT 1e7  /* max D / min D */
+#define IONODE_CMAES_STATE_SIGMA 0
+#define IONODE_CMAES_STATE_SIGMA_OLD 1
+#define IONODE_CMAES_STATE_BEST_F 2
+#define IONODE_CMAES_STATE_F_SIG 3
+#define IONODE_CMAES_STATE_UNCHANGED 4
+#define IONODE_CMAES_STATE_HSIG 5
+#define IONODE_CMAES_STATE_NFINITE 6
+#define IONODE_CMAES_STATE_FLAG 7
+#define IONODE_CMAES_STATE_ROT_C 8
+#define IONODE_CMAES_STATE_ROT_S 9
+#define IONODE_CMAES_STATE_NROT 10
+#define IONODE_CMAES_STATE_COND 11
+#define IONODE_CMAES_STATE_M 12
+#define IONODE_CMAES_RUNNING 0
+#define IONODE_CMAES_MAXITER 1
+#define IONODE_CMAES_UNCHANGED 2
+#define IONODE_CMAES_TOLX 3
+#define IONODE_CMAES_CONDITION 4
+#define IONODE_CMAES_NONFINITE 5
+
+typedef struct ionode_cmaes_desc {
+  int32_t n_run;           /* K: runs the state arrays hold */
+  int32_t n_active;        /* launch slots of this call, <= n_run */
+  int32_t lambda;          /* candidates per generation, 2 .. IONODE_CMAES_MAX_LAMBDA */
+  int32_t n_prot;          /* P: trajectories per candidate */
+  int32_t n_params;        /* NPAR: 8 (HH 2-state, NN-f, NN-d rate parameters) or 12 (6-state) */
+  int32_t n_free;          /* n */
+  int32_t log_parameters;
+  int32_t max_iter;        /* generations a run may be told */
+  int32_t unchanged_iters;
+  int32_t run_base;        /* index of the state arrays' first run among all runs of the fit (sharding): the generator sees run_base + run */
+  double unchanged_threshold, tolx;
+  int64_t seed;
+  int32_t free_idx[IONODE_LM_MAX_FREE];
+  double base[IONODE_LM_MAX_FREE];
+  double lo[IONODE_LM_MAX_FREE], hi[IONODE_LM_MAX_FREE];   /* the box, in the parameters (log_parameters: lo > 0) */
+} ionode_cmaes_desc;
+
+int ionode_cmaes_step(const ionode_cmaes_desc *d, const int32_t *active, const double *value, const int32_t *status, double *state,
+                      int32_t *flag, int32_t *iters, double *trial, void *stream);
+int ionode_cmaes_step_host(const ionode_cmaes_desc *d, const int32_t *active, const double *value, const int32_t *status, double *state,
+                           int32_t *flag, int32_t *iters, double *trial);
+/* Pure host code, for tests of the generator: the four Philox words and the two normal deviates of one draw, and the step's
+ * logarithm (finite x > 0; 0 gives -inf, x < 0 or NaN gives NaN, +inf gives +inf). */
+void ionode_cmaes_draw_host(int64_t seed, int32_t run, int32_t generation, int32_t candidate, int32_t pair, int32_t attempt,
+                            uint32_t words[4], double z[2]);
+double ionode_cmaes_log_host(double x);
+
 #ifdef __cplusplus
 }
 #endif

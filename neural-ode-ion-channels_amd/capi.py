@@ -116,6 +116,58 @@ def lm_state_views(state, nf):
     return v
 
 
+# the CMA-ES step (include/ionode.h ionode_cmaes_desc, IONODE_CMAES_*): descriptor, state layout, stop flags
+CMAES_MAX_LAMBDA, CMAES_RESAMPLES, CMAES_JACOBI_SWEEPS, CMAES_CONDITION_LIMIT = 64, 8, 30, 1e7
+(CMAES_STATE_SIGMA, CMAES_STATE_SIGMA_OLD, CMAES_STATE_BEST_F, CMAES_STATE_F_SIG, CMAES_STATE_UNCHANGED, CMAES_STATE_HSIG,
+ CMAES_STATE_NFINITE, CMAES_STATE_FLAG, CMAES_STATE_ROT_C, CMAES_STATE_ROT_S, CMAES_STATE_NROT, CMAES_STATE_COND, CMAES_STATE_M) = range(13)
+CMAES_RUNNING, CMAES_MAXITER, CMAES_UNCHANGED, CMAES_TOLX, CMAES_CONDITION, CMAES_NONFINITE = range(6)
+CMAES_FLAG_TEXT = {0: "running", 1: "generation cap", 2: "best value unchanged (PINTS' rule)", 3: "step size below tolx",
+                   4: "condition of C above the limit", 5: "fewer than mu finite values, or a non-finite state"}
+
+
+class IonodeCmaesDesc(C.Structure):
+    _fields_ = [
+        ("n_run", C.c_int32), ("n_active", C.c_int32), ("lambda", C.c_int32), ("n_prot", C.c_int32), ("n_params", C.c_int32),
+        ("n_free", C.c_int32), ("log_parameters", C.c_int32), ("max_iter", C.c_int32), ("unchanged_iters", C.c_int32),
+        ("run_base", C.c_int32), ("unchanged_threshold", C.c_double), ("tolx", C.c_double), ("seed", C.c_int64),
+        ("free_idx", C.c_int32 * LM_MAX_FREE), ("base", C.c_double * LM_MAX_FREE),
+        ("lo", C.c_double * LM_MAX_FREE), ("hi", C.c_double * LM_MAX_FREE),
+    ]
+
+
+def cmaes_default_lambda(n):
+    """Hansen's default population size 4 + floor(3 ln n)."""
+    return 4 + int(np.floor(3.0 * np.log(n)))
+
+
+def cmaes_state_doubles(n, lam):
+    """fp64 words of one run's CMA-ES state: the scalars, 8 vectors [n], 3 matrices [n][n], f and w [lam], the points u and x [lam][n]."""
+    return CMAES_STATE_M + 8 * n + 3 * n * n + 2 * lam + 2 * lam * n
+
+
+def cmaes_state_views(state, n, lam):
+    """Named views of a state array [K, cmaes_state_doubles(n, lam)] (numpy or torch): sigma, sigma_old, best_f, f_sig, unchanged,
+    hsig, nfinite, flag, cond [K]; m, m_old, pc, ps, D, best_x, yw, zw [K, n]; C, B, A [K, n, n]; f, w [K, lam]; pop, pop_x [K, lam, n]."""
+    K = state.shape[0]
+    v = {name: state[:, k] for name, k in (("sigma", CMAES_STATE_SIGMA), ("sigma_old", CMAES_STATE_SIGMA_OLD), ("best_f", CMAES_STATE_BEST_F),
+                                           ("f_sig", CMAES_STATE_F_SIG), ("unchanged", CMAES_STATE_UNCHANGED), ("hsig", CMAES_STATE_HSIG),
+                                           ("nfinite", CMAES_STATE_NFINITE), ("flag", CMAES_STATE_FLAG), ("cond", CMAES_STATE_COND))}
+    o = CMAES_STATE_M
+    for name in ("m", "m_old", "pc", "ps", "D", "best_x", "yw", "zw"):
+        v[name] = state[:, o:o + n]
+        o += n
+    for name in ("C", "B", "A"):
+        v[name] = state[:, o:o + n * n].reshape(K, n, n)
+        o += n * n
+    for name in ("f", "w"):
+        v[name] = state[:, o:o + lam]
+        o += lam
+    for name in ("pop", "pop_x"):
+        v[name] = state[:, o:o + lam * n].reshape(K, lam, n)
+        o += lam * n
+    return v
+
+
 # Every symbol of include/ionode.h: name -> (restype, argtypes); lib() applies the table, EXPORTS is its keys.
 _D, _P, _I32, _I64, _F32 = C.POINTER(IonodeDesc), C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _SOLVE = [_D] + [_P] * 12   # ionode_dopri5: d, mlp_packed .. stats, stream -- the solve family's common prefix
@@ -152,6 +204,11 @@ PROTOTYPES = {
     # d, active, sse, jtr, jtj, status, state, flag, iters, trial (, stream)
     "ionode_lm_step": (C.c_int, [C.POINTER(IonodeLmDesc)] + [_P] * 10),
     "ionode_lm_step_host": (C.c_int, [C.POINTER(IonodeLmDesc)] + [_P] * 9),
+    # d, active, value, status, state, flag, iters, trial (, stream)
+    "ionode_cmaes_step": (C.c_int, [C.POINTER(IonodeCmaesDesc)] + [_P] * 8),
+    "ionode_cmaes_step_host": (C.c_int, [C.POINTER(IonodeCmaesDesc)] + [_P] * 7),
+    "ionode_cmaes_draw_host": (None, [_I64] + [_I32] * 5 + [C.POINTER(C.c_uint32 * 4), C.POINTER(C.c_double * 2)]),
+    "ionode_cmaes_log_host": (C.c_double, [C.c_double]),
     "ionode_grad_reduce": (C.c_int, _REDUCE),
     "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
     "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),

@@ -16,7 +16,8 @@ and the candidates still running are packed into the front launch slots (the ste
 solve after at most `compact_every` further iterations.  A candidate's iterates do not depend on the others: compaction, the batch
 around it and the sharding of objective.population_fit leave its bits alone.
 
-Out of scope: the NN models (their tangent sweep is refused), CMA-ES, a noise model (plain sum of squares), sensitivities with respect to y0.
+Out of scope: the NN models (their tangent sweep is refused) and CMA-ES -- both are cmaes.py, the derivative-free sibling --,
+a noise model (plain sum of squares), sensitivities with respect to y0.
 """
 import ctypes as C
 
@@ -104,7 +105,7 @@ def levenberg_marquardt(model, x0, protocols_v, data_i, t_eval, *, base_params, 
     on the device: the best accepted point of every start; sse = inf and flag LM_NONFINITE where the start itself could not be
     evaluated.  `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature on CPU tensors; the step is then
     ionode_lm_step_host and nothing needs a GPU.  The product default has no CPU path.
-    Out of scope: NN models, CMA-ES, a noise model, y0 sensitivities (module docstring)."""
+    Out of scope: NN models and CMA-ES (both: cmaes.minimise), a noise model, y0 sensitivities (module docstring)."""
     from . import batched, sensitivity
     if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
         raise capi.IonodeError("fit.levenberg_marquardt: HH 2-state and 6-state models only (the NN models' tangent sweep is refused)")

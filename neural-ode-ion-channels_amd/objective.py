@@ -339,7 +339,8 @@ def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free
     others, so there is no communication during the fit and one all-gather of [C, len(free) + 4] at its end.  A candidate's result
     does not depend on the shard it ran in.  `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature on CPU
     tensors -- the step then runs as ionode_lm_step_host and the loop, the compaction and the all-gather need no GPU.
-    Out of scope: the NN models (their tangent sweep is refused), CMA-ES, a noise model, sensitivities with respect to y0.
+    Out of scope: the NN models (their tangent sweep is refused) and CMA-ES -- both are population_cmaes / cmaes.py --, a noise model,
+    sensitivities with respect to y0.
     """
     who = "population_fit"
     import torch.distributed as dist
@@ -384,6 +385,81 @@ def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free
     if world > 1:
         m = max(b[1] - b[0] for b in bounds_r)
         pad = torch.zeros((m, nf + 4), dtype=torch.float64, device=dev)
+        pad[: hi - lo] = out
+        parts = [torch.empty_like(pad) for _ in range(world)]
+        dist.all_gather(parts, pad, group=group)
+        out = torch.cat([parts[r][: bounds_r[r][1] - bounds_r[r][0]] for r in range(world)])
+    return out[:, :nf].contiguous(), out[:, nf].contiguous(), out[:, nf + 1].to(torch.int32), out[:, nf + 2:].to(torch.int32).contiguous()
+
+
+def population_cmaes(starts, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds=None, objective="sse",
+                     popsize=None, sigma0=0.1, scale=None, seed=0, max_iter=1000, unchanged_iters=100, unchanged_threshold=1e-3, tolx=1e-11,
+                     compact_every=4, prot_t0=0.0, prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
+                     obs_open_state_only=False, max_total_steps=1_000_000, max_step="auto", rtol=1e-7, atol=1e-9, group=None, device=None,
+                     solver=None, cost=None, model=capi.MODEL_HH2, weights=None, mlp_layers=0, mlp_width=0, weights_key=None):
+    """Batched CMA-ES (the reference's optimiser: PINTS' CMA-ES under a LogTransformation, train-d0.py:508-540): every row of starts
+    [K, len(free)] is the initial mean of an independent run, all of them advanced together (cmaes.minimise: one fused forward solve
+    of K * lambda * P trajectories and one ionode_cmaes_step launch per generation, one read of the stop flags every compact_every
+    generations).
+
+    All four models and both objective kinds ("sse": the reference's SumOfSquaresError; "sae": sums of absolute residuals); the NN
+    models take one shared weight set and `free` indexes their 8 rate parameters (NN-d's HH rates around a trained net are what
+    train-d0.py fits).  bounds = (lo, hi) in the parameters (the reference: p0 * 0.1 .. p0 * 10) or None; sigma0 = 0.1 with scale 1
+    in log parameters is the reference's sigma0 = 0.1 * p0; unchanged_iters = 100 at unchanged_threshold = 1e-3 is its stopping rule.
+    Returns (x [K, len(free)], value [K], flag [K] int32, iterations [K, 2] int32 = (generations, evaluations)) on the device: the
+    best point each run evaluated, its value (inf if none was finite), why it stopped (capi.CMAES_*: never 0) and what it cost.
+    max_step "auto" is resolved ONCE, as population_fit resolves it: grad.stable_step_cap at the upper corner of the box, or without
+    bounds over the starts; the NN models carry no such cap and take 0.
+    Sharding as population_fit (contiguous, or equal cost with `cost`); the runs of a shard need nothing from the others -- a run's
+    random numbers depend on (seed, its index among all K runs, generation, candidate, coordinate, attempt) only -- so there is no
+    communication during the fit and one all-gather of [K, len(free) + 4] at its end, padded to the largest shard as the population
+    errors are.  A run's result does not depend on the shard it ran in.  `solver` (tests only): a stand-in with batched.solve's
+    signature on CPU tensors; the step then runs as ionode_cmaes_step_host.
+    """
+    import torch.distributed as dist
+    from . import cmaes
+    D, npar = capi.n_state(model), capi.n_params(model)
+    free = [int(f) for f in free]
+    nf = len(free)
+    cand = np.asarray(starts, dtype=np.float64).reshape(-1, nf)
+    K = cand.shape[0]
+    base = np.asarray(base_params, dtype=np.float64)
+    if base.shape != (npar,) or len(y0) != D:
+        raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
+    on = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+    if cost is not None and len(cost) != K:
+        raise capi.IonodeError(f"cost has {len(cost)} entries for {K} runs: the shards would not cover the population")
+    bounds_r = [distributed.shard_bounds(K, r, world) for r in range(world)] if cost is None \
+        else distributed.shard_bounds_by_cost(cost, world)
+    lo, hi = bounds_r[rank]
+    dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
+    if isinstance(max_step, str):
+        if max_step != "auto":
+            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
+        if model in (capi.MODEL_NNF, capi.MODEL_NND):
+            max_step = 0.0
+        else:
+            corner = np.tile(base, (K, 1))
+            if bounds is not None and np.isfinite(np.asarray(bounds[1], dtype=np.float64)).all():
+                corner = corner[:1]
+                corner[:, free] = np.asarray(bounds[1], dtype=np.float64)
+            else:
+                corner[:, free] = cand
+            fin = np.isfinite(corner).all(axis=1)
+            max_step = grad.stable_step_cap(model, torch.from_numpy(corner[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
+                if fin.any() else 0.0
+    x, val, flag, iters = cmaes.minimise(model, cand[lo:hi], protocols_v, data_i, t_eval, base_params=base, free=free, log_parameters=log_parameters,
+                                         bounds=bounds, objective=objective, popsize=popsize, sigma0=sigma0, scale=scale, seed=seed,
+                                         max_iter=max_iter, unchanged_iters=unchanged_iters, unchanged_threshold=unchanged_threshold, tolx=tolx,
+                                         compact_every=compact_every, weights=weights, mlp_layers=mlp_layers, mlp_width=mlp_width,
+                                         weights_key=weights_key, prot_t0=prot_t0, prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g,
+                                         obs_e=obs_e, obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps,
+                                         max_step=float(max_step), rtol=rtol, atol=atol, device=dev, solver=solver, run_offset=lo)
+    out = torch.cat([x, val[:, None], flag.double()[:, None], iters.double()], dim=1)   # [n, nf + 4]
+    if world > 1:
+        m = max(b[1] - b[0] for b in bounds_r)
+        pad = torch.full((m, nf + 4), float("inf"), dtype=torch.float64, device=dev)
         pad[: hi - lo] = out
         parts = [torch.empty_like(pad) for _ in range(world)]
         dist.all_gather(parts, pad, group=group)
