@@ -703,6 +703,106 @@ void ionode_cmaes_draw_host(int64_t seed, int32_t run, int32_t generation, int32
                             uint32_t words[4], double z[2]);
 double ionode_cmaes_log_host(double x);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Adaptive Metropolis step for many independent chains (all four models; new symbols, ABI stays 10).
+ * What follows a fit of noisy data in the reference's workflow (noise_sigma = 0.1, train-d0.py:487-492) is posterior sampling
+ * under a Gaussian noise model.  Here K chains -- restarts for R-hat, start points, seeds -- advance together, each with P
+ * protocols.  An iteration of all chains is two launches on one stream with no host synchronisation between them: the forward
+ * solve with the fused sum of squares on the trial tensor [n_active * P][NPAR], then the step entry point below on its
+ * per-trajectory values and statuses: the TELL of that evaluation (the Metropolis decision, the adaptation, a recorded sample, the
+ * stop flags), then the PROPOSAL of the next, which overwrites the trial tensor in place.
+ *
+ * Launch slot s holds chain active[s] (active == NULL: chain s).  value / status / trial are indexed by slot -- the slot's P
+ * trajectories are rows s P .. s P + P - 1, one per protocol -- and state / flag / iters / samples by chain.
+ *
+ * The algorithm is adaptive Metropolis (Haario, Saksman, Tamminen 2001) with global adaptive scaling, as Algorithm 4 of Andrieu
+ * and Thoms, "A tutorial on adaptive MCMC" (2008).  Coordinates: the n_free free rate parameters as u_j = log x_j (log_parameters)
+ * or u_j = x_j and, with sample_sigma, one more, the last: u_sigma = log sigma (always the logarithm); n = n_free + sample_sigma <=
+ * IONODE_MCMC_MAX_DIM.  With S = sum_p value, p = 0 .. P - 1 in that order (a non-zero status on any of the P rows, or a NaN,
+ * makes S = +inf) and N = n_samples (P times the samples of a trace):
+ *   target   lp = -N u_sigma - (S / 2) exp(-2 u_sigma); without sample_sigma u_sigma = log sigma of the descriptor's sigma.  The
+ *            prior is uniform over the box [lo, hi] x [sigma_lo, sigma_hi] IN THE SEARCH SPACE (log-uniform in x under
+ *            log_parameters, log-uniform in sigma); outside the box lp = -inf.  The bounds are required to be finite.
+ *   t = 0    (iters[chain][0] == 0) the evaluation is the start's: lp becomes its log-posterior; IONODE_MCMC_NONFINITE if the
+ *            start is outside the box or lp is not finite.  Nothing is decided, nothing adapts.
+ *   tell     t >= 1: alpha = 0 if the proposal was outside the box (IONODE_MCMC_STATE_OUTSIDE, left by the previous call) or
+ *            lp_t is not finite, otherwise alpha = exp(min(lp_t - lp, 0)).  Accepted iff alpha > 0 and log w < lp_t - lp, w the
+ *            uniform below: then (u, x, lp) <- (ut, xt, lp_t) and iters[chain][1] goes up.
+ *   adapt    t >= adapt_start: k = t - adapt_start + 2 (it starts at 2: gamma = 1 would collapse C to zero), gamma =
+ *            exp(-eta log k); mu <- mu + gamma (u - mu); C <- C + gamma ((u - mu)(u - mu)^T - C) with the mu just updated,
+ *            written as a symmetric pair; log_lambda <- log_lambda + gamma (alpha - target_accept).  Before adapt_start none of
+ *            the three moves.
+ *   record   t % thin == 0 and t / thin < sample_cap: row t / thin of samples[chain] <- (x [n_free], sigma if sampled, lp): the
+ *            parameters, not the search variables.  samples may be NULL.
+ *   stop     the first that holds of IONODE_MCMC_NONFINITE (t = 0, above), IONODE_MCMC_DEGENERATE (a pivot of the factorisation
+ *            below is not a positive finite number, or log_lambda or C is not finite; the factor in the state then stays the
+ *            last good one), IONODE_MCMC_MAXITER (t >= max_iter).  A chain whose flag is not 0 is frozen: a later call changes
+ *            nothing of its state, flag or iters and writes its current x into its slot's trial rows.
+ *   propose  L L^T = exp(log_lambda) (C + epsilon I) by Cholesky, every call; ut = u + L z.  A ut outside the box is not redrawn:
+ *            the OUTSIDE word is set and the slot's trial rows get the current x (its solve is wasted, its tell rejects without
+ *            using the value).  Otherwise xt = exp(ut) clamped into [lo, hi] (the library's deterministic exp) or xt = ut, and
+ *            the P trial rows are base[] with the free columns replaced by xt.  Sigma never enters the rows.
+ *
+ * Random numbers: the CMA-ES step's generator, unchanged -- Philox4x32-10, key (low, high word of seed), the same 53-bit
+ * uniforms, PPND16 and logarithm.  The proposal evaluated at iteration t takes its deviates from the counters (chain_base + chain,
+ * t, 0, pair): coordinates 2 pair and 2 pair + 1; the acceptance uniform of iteration t is the first uniform of (chain_base +
+ * chain, t, 1, 0).  A draw is a pure function of its indices: compaction, the chain's company and the host mirror see the same.
+ *
+ * state [n_chain][IONODE_MCMC_STATE_U + 5 n + 2 n^2] fp64, per chain: [IONODE_MCMC_STATE_LP] lp, [IONODE_MCMC_STATE_LOG_LAMBDA]
+ * log_lambda, [IONODE_MCMC_STATE_OUTSIDE] 1 if the proposal in flight left the box, else 0, [IONODE_MCMC_STATE_ALPHA] the last
+ * alpha; then from IONODE_MCMC_STATE_U on: u, ut, x, xt, mu [n each; with sample_sigma the last entry of x and xt is sigma]; C
+ * [n][n], exactly symmetric; L [n][n], lower triangular, row-major both.
+ * To start a chain the caller sets u = ut = mu = the start in the search space, x = xt = the start, C = diag(s_j^2), the rest 0,
+ * flag = 0, iters = 0, and writes the start into the slot's trial rows.  iters [n_chain][2]: the iteration the chain is at (the
+ * t of its next call; a stopped chain keeps the t it stopped at: max_iter decisions for IONODE_MCMC_MAXITER), accepted proposals.
+ *
+ * Execution model: one lane per chain, n a compile-time constant; no LDS, no cross-lane operation, no atomic, every sum in one
+ * written order.  The host entry point runs the same per-chain routine on host pointers, no HIP call: its results equal the
+ * kernel's bit for bit, and a chain's results do not depend on the other chains of the call or on its slot.
+ * Refusals, all before anything is touched, text in the gradient path's error string: IONODE_ERR_ARG for a NULL descriptor or
+ * buffer (active and samples may be NULL), n_free or n_params outside 1 .. IONODE_LM_MAX_FREE, a free index outside n_params,
+ * lo > hi (or a NaN bound), an infinite bound, non-positive bounds with log_parameters, sigma_lo <= 0 or sigma_lo > sigma_hi (or an
+ * infinite sigma_hi) with sample_sigma, sigma <= 0 without it, eta outside (0.5, 1], target_accept outside (0, 1), thin < 1, or
+ * n_chain / n_active / n_prot / max_iter < 1 or n_active > n_chain.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define IONODE_MCMC_MAX_DIM 13
+#define IONODE_MCMC_STATE_LP 0
+#define IONODE_MCMC_STATE_LOG_LAMBDA 1
+#define IONODE_MCMC_STATE_OUTSIDE 2
+#define IONODE_MCMC_STATE_ALPHA 3
+#define IONODE_MCMC_STATE_U 4
+#define IONODE_MCMC_RUNNING 0
+#define IONODE_MCMC_MAXITER 1
+#define IONODE_MCMC_DEGENERATE 2
+#define IONODE_MCMC_NONFINITE 3
+
+typedef struct ionode_mcmc_desc {
+  int32_t n_chain;         /* K: chains the state arrays hold */
+  int32_t n_active;        /* launch slots of this call, <= n_chain */
+  int32_t n_prot;          /* P: trajectories per chain */
+  int32_t n_params;        /* NPAR: 8 (HH 2-state, NN-f, NN-d rate parameters) or 12 (6-state) */
+  int32_t n_free;          /* nf */
+  int32_t log_parameters;
+  int32_t sample_sigma;    /* 1: log sigma is the last coordinate, within [sigma_lo, sigma_hi]; 0: sigma is fixed */
+  int32_t max_iter;        /* Metropolis decisions a chain makes */
+  int32_t adapt_start;     /* first iteration that adapts */
+  int32_t thin;            /* every thin-th iteration is recorded */
+  int32_t sample_cap;      /* rows of samples[chain] */
+  int32_t chain_base;      /* index of the state arrays' first chain among all chains of the run (sharding): the generator sees chain_base + chain */
+  int64_t seed;
+  double n_samples;        /* N: residuals behind S, P times the samples of a trace */
+  double sigma, sigma_lo, sigma_hi;
+  double eta, target_accept, epsilon;
+  int32_t free_idx[IONODE_LM_MAX_FREE];
+  double base[IONODE_LM_MAX_FREE];
+  double lo[IONODE_LM_MAX_FREE], hi[IONODE_LM_MAX_FREE];   /* the box, in the parameters: finite (log_parameters: lo > 0) */
+} ionode_mcmc_desc;
+
+int ionode_mcmc_step(const ionode_mcmc_desc *d, const int32_t *active, const double *value, const int32_t *status, double *state,
+                     int32_t *flag, int32_t *iters, double *trial, double *samples, void *stream);
+int ionode_mcmc_step_host(const ionode_mcmc_desc *d, const int32_t *active, const double *value, const int32_t *status, double *state,
+                          int32_t *flag, int32_t *iters, double *trial, double *samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -168,6 +168,49 @@ def cmaes_state_views(state, n, lam):
     return v
 
 
+# the adaptive-Metropolis step (include/ionode.h ionode_mcmc_desc, IONODE_MCMC_*): descriptor, state layout, stop flags
+MCMC_MAX_DIM = 13
+MCMC_STATE_LP, MCMC_STATE_LOG_LAMBDA, MCMC_STATE_OUTSIDE, MCMC_STATE_ALPHA, MCMC_STATE_U = range(5)
+MCMC_RUNNING, MCMC_MAXITER, MCMC_DEGENERATE, MCMC_NONFINITE = range(4)
+MCMC_FLAG_TEXT = {0: "running", 1: "iteration cap", 2: "proposal covariance not positive definite, or a non-finite adaptation state",
+                  3: "start outside the box, or its log-posterior not finite"}
+
+
+class IonodeMcmcDesc(C.Structure):
+    _fields_ = [
+        ("n_chain", C.c_int32), ("n_active", C.c_int32), ("n_prot", C.c_int32), ("n_params", C.c_int32), ("n_free", C.c_int32),
+        ("log_parameters", C.c_int32), ("sample_sigma", C.c_int32), ("max_iter", C.c_int32), ("adapt_start", C.c_int32),
+        ("thin", C.c_int32), ("sample_cap", C.c_int32), ("chain_base", C.c_int32), ("seed", C.c_int64),
+        ("n_samples", C.c_double), ("sigma", C.c_double), ("sigma_lo", C.c_double), ("sigma_hi", C.c_double),
+        ("eta", C.c_double), ("target_accept", C.c_double), ("epsilon", C.c_double),
+        ("free_idx", C.c_int32 * LM_MAX_FREE), ("base", C.c_double * LM_MAX_FREE),
+        ("lo", C.c_double * LM_MAX_FREE), ("hi", C.c_double * LM_MAX_FREE),
+    ]
+
+
+def mcmc_state_doubles(n):
+    """fp64 words of one chain's adaptive-Metropolis state: lp, log_lambda, the outside word, alpha, then u, ut, x, xt, mu [n] and
+    C, L [n][n]; n = the free parameters plus one if sigma is sampled."""
+    return MCMC_STATE_U + 5 * n + 2 * n * n
+
+
+def mcmc_state_views(state, nf, sample_sigma):
+    """Named views of a state array [K, mcmc_state_doubles(n)] (numpy or torch), n = nf + (1 if sample_sigma else 0): lp, log_lambda,
+    outside, alpha [K]; u, ut, x, xt, mu [K, n]; C, L [K, n, n]."""
+    n = nf + (1 if sample_sigma else 0)
+    K = state.shape[0]
+    v = {"lp": state[:, MCMC_STATE_LP], "log_lambda": state[:, MCMC_STATE_LOG_LAMBDA], "outside": state[:, MCMC_STATE_OUTSIDE],
+         "alpha": state[:, MCMC_STATE_ALPHA]}
+    o = MCMC_STATE_U
+    for name in ("u", "ut", "x", "xt", "mu"):
+        v[name] = state[:, o:o + n]
+        o += n
+    for name in ("C", "L"):
+        v[name] = state[:, o:o + n * n].reshape(K, n, n)
+        o += n * n
+    return v
+
+
 # Every symbol of include/ionode.h: name -> (restype, argtypes); lib() applies the table, EXPORTS is its keys.
 _D, _P, _I32, _I64, _F32 = C.POINTER(IonodeDesc), C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _SOLVE = [_D] + [_P] * 12   # ionode_dopri5: d, mlp_packed .. stats, stream -- the solve family's common prefix
@@ -209,6 +252,9 @@ PROTOTYPES = {
     "ionode_cmaes_step_host": (C.c_int, [C.POINTER(IonodeCmaesDesc)] + [_P] * 7),
     "ionode_cmaes_draw_host": (None, [_I64] + [_I32] * 5 + [C.POINTER(C.c_uint32 * 4), C.POINTER(C.c_double * 2)]),
     "ionode_cmaes_log_host": (C.c_double, [C.c_double]),
+    # d, active, value, status, state, flag, iters, trial, samples (, stream)
+    "ionode_mcmc_step": (C.c_int, [C.POINTER(IonodeMcmcDesc)] + [_P] * 9),
+    "ionode_mcmc_step_host": (C.c_int, [C.POINTER(IonodeMcmcDesc)] + [_P] * 8),
     "ionode_grad_reduce": (C.c_int, _REDUCE),
     "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
     "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),

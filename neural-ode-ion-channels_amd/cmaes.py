@@ -19,7 +19,8 @@ equals the kernel bit for bit.
 
 The derivative-based sibling is fit.py (Levenberg-Marquardt: HH 2-state and 6-state, sum of squares only).
 Out of scope: bit-compatibility with PINTS or the cma package (boundary transform, penalties), negative weights, restarts with a
-growing population, variants for more than 12 variables, fitting MLP weights, a noise model.
+growing population, variants for more than 12 variables, fitting MLP weights.  A noise model and the posterior around a fit are mcmc.py
+(adaptive Metropolis on the same fused sums: ionode_mcmc_step, objective.population_mcmc).
 """
 import ctypes as C
 

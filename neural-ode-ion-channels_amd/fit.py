@@ -17,7 +17,8 @@ solve after at most `compact_every` further iterations.  A candidate's iterates 
 around it and the sharding of objective.population_fit leave its bits alone.
 
 Out of scope: the NN models (their tangent sweep is refused) and CMA-ES -- both are cmaes.py, the derivative-free sibling --,
-a noise model (plain sum of squares), sensitivities with respect to y0.
+sensitivities with respect to y0.  A noise model (the fit minimises the plain sum of squares) and the posterior around a fit
+are mcmc.py: adaptive Metropolis, objective.population_mcmc.
 """
 import ctypes as C
 
@@ -105,7 +106,7 @@ def levenberg_marquardt(model, x0, protocols_v, data_i, t_eval, *, base_params, 
     on the device: the best accepted point of every start; sse = inf and flag LM_NONFINITE where the start itself could not be
     evaluated.  `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature on CPU tensors; the step is then
     ionode_lm_step_host and nothing needs a GPU.  The product default has no CPU path.
-    Out of scope: NN models and CMA-ES (both: cmaes.minimise), a noise model, y0 sensitivities (module docstring)."""
+    Out of scope: NN models and CMA-ES (both: cmaes.minimise), y0 sensitivities (module docstring); a noise model is mcmc.sample."""
     from . import batched, sensitivity
     if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
         raise capi.IonodeError("fit.levenberg_marquardt: HH 2-state and 6-state models only (the NN models' tangent sweep is refused)")

@@ -339,8 +339,8 @@ def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free
     others, so there is no communication during the fit and one all-gather of [C, len(free) + 4] at its end.  A candidate's result
     does not depend on the shard it ran in.  `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature on CPU
     tensors -- the step then runs as ionode_lm_step_host and the loop, the compaction and the all-gather need no GPU.
-    Out of scope: the NN models (their tangent sweep is refused) and CMA-ES -- both are population_cmaes / cmaes.py --, a noise model,
-    sensitivities with respect to y0.
+    Out of scope: the NN models (their tangent sweep is refused) and CMA-ES -- both are population_cmaes / cmaes.py --, sensitivities with
+    respect to y0.  A noise model and the posterior around a fit are population_mcmc / mcmc.py.
     """
     who = "population_fit"
     import torch.distributed as dist
@@ -465,3 +465,82 @@ def population_cmaes(starts, protocols_v, data_i, t_eval, *, base_params, free=(
         dist.all_gather(parts, pad, group=group)
         out = torch.cat([parts[r][: bounds_r[r][1] - bounds_r[r][0]] for r in range(world)])
     return out[:, :nf].contiguous(), out[:, nf].contiguous(), out[:, nf + 1].to(torch.int32), out[:, nf + 2:].to(torch.int32).contiguous()
+
+
+def population_mcmc(starts, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds, sigma=None,
+                    sigma_bounds=None, scale=None, seed=0, max_iter=10000, adapt_start=200, thin=1, eta=0.6, target_accept=0.234,
+                    epsilon=1e-12, compact_every=64, prot_t0=0.0, prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
+                    obs_open_state_only=False, max_total_steps=1_000_000, max_step="auto", rtol=1e-7, atol=1e-9, group=None, device=None,
+                    solver=None, cost=None, model=capi.MODEL_HH2, weights=None, mlp_layers=0, mlp_width=0, weights_key=None):
+    """Batched adaptive Metropolis (what follows a fit of noisy data in the reference's workflow: the posterior under a Gaussian noise
+    model): every row of starts [K, len(free)] (or [K, len(free) + 1], the last column sigma's start, when sigma is sampled) is the
+    start of an independent chain, all of them advanced together (mcmc.sample: one fused forward solve of K * P trajectories and one
+    ionode_mcmc_step launch per iteration, one read of the stop flags every compact_every iterations).
+
+    All four models; the NN models take one shared weight set and `free` indexes their 8 rate parameters.  bounds = (lo, hi) in the
+    parameters, required and finite: the prior is uniform over the box in the search space -- LOG-UNIFORM in the parameters with
+    log_parameters (the default).  Exactly one of sigma (fixed noise level) and sigma_bounds (sigma sampled, log-uniform within them).
+    Returns (samples [K, R, n + 1], accept_rate [K], flag [K] int32, iterations [K, 2] int32 = (iterations, accepted)) on the device,
+    as mcmc.sample does; mcmc.rhat turns the samples into Gelman and Rubin's R-hat.
+    max_step "auto" is resolved ONCE, as population_cmaes resolves it: grad.stable_step_cap at the upper corner of the box; the NN
+    models carry no such cap and take 0.
+    Sharding as population_cmaes (contiguous, or equal cost with `cost`); the chains of a shard need nothing from the others -- a
+    chain's random numbers depend on (seed, its index among all K chains, iteration, purpose, coordinate) only -- so there is no
+    communication during the run and one all-gather at its end, padded to the largest shard.  A chain's samples do not depend on
+    the shard it ran in.  `solver` (tests only): a stand-in with batched.solve's signature on CPU tensors; the step then runs as
+    ionode_mcmc_step_host.
+    """
+    import torch.distributed as dist
+    from . import mcmc
+    D, npar = capi.n_state(model), capi.n_params(model)
+    free = [int(f) for f in free]
+    nf = len(free)
+    n = nf + int(sigma is None)
+    cand = np.asarray(starts, dtype=np.float64)
+    if cand.ndim != 2:
+        cand = cand.reshape(-1, nf)
+    K = cand.shape[0]
+    base = np.asarray(base_params, dtype=np.float64)
+    if base.shape != (npar,) or len(y0) != D:
+        raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
+    if bounds is None:
+        raise capi.IonodeError("population_mcmc: bounds = (lo, hi) are required: the box is the prior")
+    if (sigma is None) == (sigma_bounds is None):
+        raise capi.IonodeError("population_mcmc: exactly one of sigma (fixed noise) and sigma_bounds (sampled noise) must be given")
+    on = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+    if cost is not None and len(cost) != K:
+        raise capi.IonodeError(f"cost has {len(cost)} entries for {K} chains: the shards would not cover the population")
+    bounds_r = [distributed.shard_bounds(K, r, world) for r in range(world)] if cost is None \
+        else distributed.shard_bounds_by_cost(cost, world)
+    lo, hi = bounds_r[rank]
+    dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
+    if isinstance(max_step, str):
+        if max_step != "auto":
+            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
+        if model in (capi.MODEL_NNF, capi.MODEL_NND):
+            max_step = 0.0
+        else:
+            corner = base[None].copy()
+            corner[:, free] = np.asarray(bounds[1], dtype=np.float64)
+            max_step = grad.stable_step_cap(model, torch.from_numpy(corner), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
+                if np.isfinite(corner).all() else 0.0
+    smp, rate, flag, iters = mcmc.sample(model, cand[lo:hi], protocols_v, data_i, t_eval, base_params=base, free=free, log_parameters=log_parameters,
+                                         bounds=bounds, sigma=sigma, sigma_bounds=sigma_bounds, scale=scale, seed=seed, max_iter=max_iter,
+                                         adapt_start=adapt_start, thin=thin, eta=eta, target_accept=target_accept, epsilon=epsilon,
+                                         compact_every=compact_every, weights=weights, mlp_layers=mlp_layers, mlp_width=mlp_width,
+                                         weights_key=weights_key, prot_t0=prot_t0, prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g,
+                                         obs_e=obs_e, obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps,
+                                         max_step=float(max_step), rtol=rtol, atol=atol, device=dev, solver=solver, chain_offset=lo)
+    R = smp.shape[1]
+    out = torch.cat([smp.reshape(hi - lo, R * (n + 1)), rate[:, None], flag.double()[:, None], iters.double()], dim=1)   # [chains, R (n + 1) + 4]
+    if world > 1:
+        m = max(b[1] - b[0] for b in bounds_r)
+        pad = torch.full((m, R * (n + 1) + 4), float("inf"), dtype=torch.float64, device=dev)
+        pad[: hi - lo] = out
+        parts = [torch.empty_like(pad) for _ in range(world)]
+        dist.all_gather(parts, pad, group=group)
+        out = torch.cat([parts[r][: bounds_r[r][1] - bounds_r[r][0]] for r in range(world)])
+    w = R * (n + 1)
+    return (out[:, :w].reshape(-1, R, n + 1).contiguous(), out[:, w].contiguous(), out[:, w + 1].to(torch.int32),
+            out[:, w + 2:].to(torch.int32).contiguous())
