@@ -22,12 +22,10 @@ Out of scope: bit-compatibility with PINTS or the cma package (boundary transfor
 growing population, variants for more than 12 variables, fitting MLP weights.  A noise model and the posterior around a fit are mcmc.py
 (adaptive Metropolis on the same fused sums: ionode_mcmc_step, objective.population_mcmc).
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, steploop
 
 FLAG_TEXT = capi.CMAES_FLAG_TEXT
 
@@ -42,15 +40,7 @@ def cmaes_desc(n_run, popsize, n_prot, n_params, free, base_params, *, log_param
                              log_parameters=int(bool(log_parameters)), max_iter=int(max_iter), unchanged_iters=int(unchanged_iters),
                              unchanged_threshold=float(unchanged_threshold), tolx=float(tolx), seed=int(seed))
     setattr(d, "lambda", lam)
-    none_lo = np.finfo(np.float64).tiny if log_parameters else -np.inf
-    lo = np.full(nf, none_lo) if lo is None else np.asarray(lo, dtype=np.float64).reshape(-1)
-    hi = np.full(nf, np.inf) if hi is None else np.asarray(hi, dtype=np.float64).reshape(-1)
-    base = np.asarray(base_params, dtype=np.float64).reshape(-1)
-    for j in range(min(nf, capi.LM_MAX_FREE)):
-        d.free_idx[j], d.lo[j], d.hi[j] = int(free[j]), float(lo[j]), float(hi[j])
-    for i in range(min(base.size, capi.LM_MAX_FREE)):
-        d.base[i] = float(base[i])
-    return d
+    return steploop.fill_box(d, free, base_params, lo, hi)
 
 
 def cmaes_init(x0, desc, sigma0=0.1, scale=None):
@@ -69,9 +59,7 @@ def cmaes_init(x0, desc, sigma0=0.1, scale=None):
     v["sigma"][:], v["sigma_old"][:], v["best_f"][:], v["f_sig"][:] = float(sigma0), float(sigma0), np.inf, np.inf
     v["m"][:], v["m_old"][:], v["best_x"][:], v["D"][:] = u0, u0, x0, s
     v["C"][:], v["B"][:] = np.diag(s * s), np.eye(nf)
-    params = np.tile(np.array(desc.base[:desc.n_params]), (K, 1))
-    params[:, list(desc.free_idx[:nf])] = x0
-    return state, np.zeros(K, dtype=np.int32), np.zeros((K, 2), dtype=np.int32), np.repeat(params, lam * desc.n_prot, axis=0)
+    return state, np.zeros(K, dtype=np.int32), np.zeros((K, 2), dtype=np.int32), steploop.trial_rows(desc, x0, lam * desc.n_prot)
 
 
 def cmaes_step(desc, active, value, status, state, flag, iters, trial):
@@ -85,18 +73,7 @@ def cmaes_step(desc, active, value, status, state, flag, iters, trial):
             ("state", state, torch.float64, (desc.n_run, capi.cmaes_state_doubles(nf, lam))), ("flag", flag, torch.int32, (desc.n_run,)),
             ("iters", iters, torch.int32, (desc.n_run, 2)), ("trial", trial, torch.float64, (rows, npar))) \
         + ((("active", active, torch.int32, (n_active,)),) if active is not None else ())
-    dev = state.device
-    for name, t, dtype, shape in want:
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise capi.IonodeError(f"cmaes_step: {name}: expected a contiguous {dtype} tensor {shape} on {dev}")
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
-    args = (C.byref(desc), ptr(active), ptr(value), ptr(status), ptr(state), ptr(flag), ptr(iters), ptr(trial))
-    if dev.type == "cuda":
-        rc = capi.lib().ionode_cmaes_step(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    else:
-        rc = capi.lib().ionode_cmaes_step_host(*args)
-    if rc != 0:
-        raise capi.IonodeError(f"ionode_cmaes_step failed ({rc}): {capi.lib().ionode_grad_last_error().decode()}")
+    steploop.step_call("cmaes", desc, state.device, want, (active, value, status, state, flag, iters, trial))
 
 
 def minimise(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds=None, objective="sse",
@@ -144,17 +121,11 @@ def minimise(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1,
                       unchanged_iters=unchanged_iters, unchanged_threshold=unchanged_threshold, tolx=tolx, seed=seed)
     lam = getattr(desc, "lambda")
     if K == 0:
-        return (torch.zeros((0, nf), dtype=torch.float64, device=dev), torch.zeros((0,), dtype=torch.float64, device=dev),
-                torch.zeros((0,), dtype=torch.int32, device=dev), torch.zeros((0, 2), dtype=torch.int32, device=dev))
+        return steploop.empty_result((nf,), dev)
     desc.run_base = int(run_offset)   # the generator's run index: a shard's runs draw what they draw in the whole population
     state, flag, iters, trial = (torch.from_numpy(a).to(dev) for a in cmaes_init(x0, desc, sigma0, scale))
-    pv = torch.as_tensor(np.asarray(protocols_v), dtype=torch.float64, device=dev).contiguous()
-    te = torch.as_tensor(np.asarray(t_eval), dtype=torch.float64, device=dev).contiguous()
-    ref = torch.as_tensor(np.asarray(data_i), dtype=torch.float64, device=dev).contiguous()
-    pot = torch.from_numpy(np.tile(np.arange(P, dtype=np.int32), K * lam)).to(dev)      # trajectory = (slot * lambda + k) * P + protocol
-    y0t = torch.tensor([list(y0)], dtype=state_dtype, device=dev).expand(K * lam * P, D).contiguous()
+    pv, te, ref, pot, y0t = steploop.problem_tensors(protocols_v, t_eval, data_i, y0, K * lam * P, state_dtype, dev)
     mlp = {} if weights is None else dict(weights=weights, mlp_layers=mlp_layers, mlp_width=mlp_width, weights_key=weights_key)
-    own = torch.arange(K, dtype=torch.int32, device=dev)
     active, n_act = None, K
     every = int(compact_every or 0)
     value = torch.zeros((K * lam * P,), dtype=torch.float64, device=dev)      # the first step reads nothing of these
@@ -164,13 +135,10 @@ def minimise(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1,
         if callback is not None:
             callback(it, state, flag, iters)
         if every and it % every == 0 and it:   # the one read: who is still running
-            slots = own if active is None else active
-            keep = torch.nonzero(flag[slots.long()] == capi.CMAES_RUNNING).reshape(-1)   # positions among the current slots, ascending
-            if keep.numel() == 0:
+            left = steploop.compact(flag, active, n_act, trial, capi.CMAES_RUNNING)
+            if left is None:
                 break
-            if keep.numel() < n_act:
-                trial = trial.reshape(n_act, lam * P * npar)[keep].reshape(-1, npar).contiguous()
-                active, n_act = slots[keep].to(torch.int32).contiguous(), int(keep.numel())
+            active, n_act, trial = left
         if it == int(max_iter):
             break
         rows = n_act * lam * P

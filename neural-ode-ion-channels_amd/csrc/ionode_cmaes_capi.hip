@@ -2,55 +2,34 @@
 // phases' by-value arguments (the box's logarithms and the strategy constants are formed here, on the host, for the kernel and the
 // mirror alike), the launch and the host mirror.  A unit of its own: the other units compile to what they did.
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
-#include <cstring>
 
 #include "ionode_cmaes.hpp"
+#include "ionode_step_capi.hpp"
 
 namespace {
 
-// The message goes where the gradient path's and the Levenberg-Marquardt step's go (ionode_lm_capi.hip refuse()).
-constexpr size_t kGradErrBytes = 256;
-__attribute__((format(printf, 2, 3))) int refuse(int rc, const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(const_cast<char *>(ionode_grad_last_error()), kGradErrBytes, fmt, ap);
-  va_end(ap);
-  return rc;
-}
+using ionode::refuse;
 
 int cmaes_args(const char *who, const ionode_cmaes_desc *d, const int32_t *active, const double *value, const int32_t *status, double *state,
                int32_t *flag, int32_t *iters, double *trial, ionode::CmArgs &a) {
   using ionode::cm_log;
-  if (!d) return refuse(IONODE_ERR_ARG, "%s: null descriptor", who);
-  if (!value || !status || !state || !flag || !iters || !trial)
-    return refuse(IONODE_ERR_ARG, "%s: required buffer is NULL (value, status, state, flag, iters, trial)", who);
-  if (d->n_free < 1 || d->n_free > IONODE_LM_MAX_FREE) return refuse(IONODE_ERR_ARG, "%s: n_free = %d outside 1 .. %d", who, (int)d->n_free, IONODE_LM_MAX_FREE);
-  if (d->lambda < 2 || d->lambda > IONODE_CMAES_MAX_LAMBDA)
-    return refuse(IONODE_ERR_ARG, "%s: lambda = %d outside 2 .. %d", who, (int)d->lambda, IONODE_CMAES_MAX_LAMBDA);
-  if (d->n_params < 1 || d->n_params > IONODE_LM_MAX_FREE)
-    return refuse(IONODE_ERR_ARG, "%s: n_params = %d outside 1 .. %d", who, (int)d->n_params, IONODE_LM_MAX_FREE);
-  if (d->n_run < 1 || d->n_active < 1 || d->n_active > d->n_run || d->n_prot < 1 || d->max_iter < 1 || d->unchanged_iters < 1)
-    return refuse(IONODE_ERR_ARG, "%s: n_run, n_active <= n_run, n_prot, max_iter and unchanged_iters must be positive", who);
+  const int rc = ionode::step_box(
+      who, d, value && status && state && flag && iters && trial, "value, status, state, flag, iters, trial", a,
+      [&] {
+        if (d->lambda < 2 || d->lambda > IONODE_CMAES_MAX_LAMBDA)
+          return refuse(IONODE_ERR_ARG, "%s: lambda = %d outside 2 .. %d", who, (int)d->lambda, IONODE_CMAES_MAX_LAMBDA);
+        if (const int r = ionode::step_n_params(who, d->n_params)) return r;
+        if (d->n_run < 1 || d->n_active < 1 || d->n_active > d->n_run || d->n_prot < 1 || d->max_iter < 1 || d->unchanged_iters < 1)
+          return refuse(IONODE_ERR_ARG, "%s: n_run, n_active <= n_run, n_prot, max_iter and unchanged_iters must be positive", who);
+        return IONODE_OK;
+      },
+      ionode::no_bound_rule);
+  if (rc != IONODE_OK) return rc;
   const bool lg = d->log_parameters != 0;
-  memset(&a, 0, sizeof a);
-  for (int j = 0; j < d->n_free; ++j) {
-    if (d->free_idx[j] < 0 || d->free_idx[j] >= d->n_params)
-      return refuse(IONODE_ERR_ARG, "%s: free index %d outside the model's %d parameters", who, (int)d->free_idx[j], (int)d->n_params);
-    if (!(d->lo[j] <= d->hi[j])) return refuse(IONODE_ERR_ARG, "%s: bounds of free parameter %d: lo > hi (or NaN)", who, j);
-    if (lg && !(d->lo[j] > 0.0)) return refuse(IONODE_ERR_ARG, "%s: log_parameters needs positive bounds (free parameter %d)", who, j);
-    a.free_idx[j] = d->free_idx[j];
-    a.xlo[j] = d->lo[j];
-    a.xhi[j] = d->hi[j];
-    a.ulo[j] = lg ? std::log(d->lo[j]) : d->lo[j];
-    a.uhi[j] = lg ? std::log(d->hi[j]) : d->hi[j];
-  }
-  for (int i = 0; i < d->n_params; ++i) a.base[i] = d->base[i];
   a.K = d->n_run; a.n_active = d->n_active; a.lam = d->lambda; a.mu = d->lambda / 2; a.P = d->n_prot; a.NPAR = d->n_params;
   a.n = d->n_free; a.log_p = lg ? 1 : 0; a.max_iter = d->max_iter; a.unchanged_iters = d->unchanged_iters; a.run_base = d->run_base;
   a.unchanged_threshold = d->unchanged_threshold; a.tolx = d->tolx;
-  a.seed_lo = (uint32_t)((uint64_t)d->seed & 0xFFFFFFFFull); a.seed_hi = (uint32_t)((uint64_t)d->seed >> 32);
+  ionode::step_seed(d->seed, a.seed_lo, a.seed_hi);
   // the strategy constants (ionode_cmaes.hpp's head), sums in index order
   const double n = (double)a.n;
   a.ln_mu_half = cm_log((double)a.mu + 0.5);
@@ -87,9 +66,7 @@ int ionode_cmaes_step(const ionode_cmaes_desc *d, const int32_t *active, const d
   const int rc = cmaes_args("ionode_cmaes_step", d, active, value, status, state, flag, iters, trial, a);
   if (rc != IONODE_OK) return rc;
   ionode::launch_cmaes_step(a, reinterpret_cast<hipStream_t>(stream));
-  const hipError_t err = hipGetLastError();
-  if (err != hipSuccess) return refuse(IONODE_ERR_LAUNCH, "ionode_cmaes_step: %s", hipGetErrorString(err));
-  return IONODE_OK;
+  return ionode::step_launched("ionode_cmaes_step");
 }
 
 int ionode_cmaes_step_host(const ionode_cmaes_desc *d, const int32_t *active, const double *value, const int32_t *status, double *state,
@@ -103,7 +80,8 @@ int ionode_cmaes_step_host(const ionode_cmaes_desc *d, const int32_t *active, co
 
 void ionode_cmaes_draw_host(int64_t seed, int32_t run, int32_t generation, int32_t candidate, int32_t pair, int32_t attempt,
                             uint32_t words[4], double z[2]) {
-  const uint32_t lo = (uint32_t)((uint64_t)seed & 0xFFFFFFFFull), hi = (uint32_t)((uint64_t)seed >> 32);
+  uint32_t lo, hi;
+  ionode::step_seed(seed, lo, hi);
   uint32_t w[4];
   ionode::cm_philox((uint32_t)run, (uint32_t)generation, (uint32_t)candidate, (uint32_t)pair + 65536u * (uint32_t)attempt, lo, hi, w);
   for (int i = 0; i < 4; ++i) words[i] = w[i];

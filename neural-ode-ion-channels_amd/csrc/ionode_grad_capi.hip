@@ -10,16 +10,24 @@
 #include "ionode_host.hpp"
 #include "ionode_tangent.hpp"
 
-namespace {
+#include "ionode_step_capi.hpp"
 
+namespace {
 thread_local char g_gerr[256] = "";
-__attribute__((format(printf, 2, 3))) int refuse(int rc, const char *fmt, ...) {   // sets ionode_grad_last_error(), returns rc
+}  // namespace
+
+// sets ionode_grad_last_error(), returns rc (declared in ionode_step_capi.hpp: the optimiser steps' units refuse through it too)
+int ionode::refuse(int rc, const char *fmt, ...) {
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_gerr, sizeof g_gerr, fmt, ap);
   va_end(ap);
   return rc;
 }
+
+namespace {
+
+using ionode::refuse;
 void gerr(const char *m) { refuse(0, "%s", m); }
 
 inline int np_of(int N) { return 16 * ((N + 15) / 16); }

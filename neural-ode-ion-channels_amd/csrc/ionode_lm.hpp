@@ -36,10 +36,10 @@
 #include <stdint.h>
 
 #include "../../include/ionode.h"
+#include "ionode_step_math.hpp"
 
 namespace ionode {
 
-constexpr int kLmMaxFree = IONODE_LM_MAX_FREE;
 constexpr int kLmRetries = IONODE_LM_RETRIES;
 constexpr double kLmFloorRel = IONODE_LM_FLOOR_REL;
 constexpr double kLmFloorAbs = IONODE_LM_FLOOR_ABS;
@@ -72,37 +72,6 @@ __host__ __device__ constexpr int lm_off_ut(int nf) { return IONODE_LM_STATE_U +
 __host__ __device__ constexpr int lm_off_xt(int nf) { return IONODE_LM_STATE_U + 4 * nf; }
 __host__ __device__ constexpr int lm_off_delta(int nf) { return IONODE_LM_STATE_U + 5 * nf; }
 __host__ __device__ constexpr int lm_off_h(int nf) { return IONODE_LM_STATE_U + 6 * nf; }
-
-__host__ __device__ inline double lm_inf() { return __builtin_inf(); }
-__host__ __device__ inline bool lm_finite(double x) { return __builtin_fabs(x) < __builtin_inf(); }   // false for NaN
-__host__ __device__ inline double lm_pow2i(int k) { return __builtin_bit_cast(double, (long long)(k + 1023) << 52); }
-
-// det_exp (ionode_math.hpp), operation for operation, compiled for both sides
-__host__ __device__ inline double lm_exp(double x) {
-  if (x != x) return x;
-  if (x > 709.782712893384) return __builtin_inf();
-  if (x < -745.1332191019412) return 0.0;
-  const double kf = __builtin_rint(x * 0x1.71547652b82fep+0);
-  double r = __builtin_fma(-kf, 0x1.62e42fee00000p-1, x);
-  r = __builtin_fma(-kf, 0x1.a39ef35793c76p-33, r);
-  double p = 1.0 / 6227020800.0;
-  p = __builtin_fma(p, r, 1.0 / 479001600.0);
-  p = __builtin_fma(p, r, 1.0 / 39916800.0);
-  p = __builtin_fma(p, r, 1.0 / 3628800.0);
-  p = __builtin_fma(p, r, 1.0 / 362880.0);
-  p = __builtin_fma(p, r, 1.0 / 40320.0);
-  p = __builtin_fma(p, r, 1.0 / 5040.0);
-  p = __builtin_fma(p, r, 1.0 / 720.0);
-  p = __builtin_fma(p, r, 1.0 / 120.0);
-  p = __builtin_fma(p, r, 1.0 / 24.0);
-  p = __builtin_fma(p, r, 1.0 / 6.0);
-  p = __builtin_fma(p, r, 0.5);
-  p = __builtin_fma(p, r, 1.0);
-  p = __builtin_fma(p, r, 1.0);
-  const int k = (int)kf;
-  const int k1 = k / 2;
-  return (p * lm_pow2i(k1)) * lm_pow2i(k - k1);
-}
 
 // the candidate's P rows of the trial tensor: the base parameters with the free columns replaced by xs[0 .. NF)
 template <int NF>

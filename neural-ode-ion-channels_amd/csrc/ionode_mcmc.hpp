@@ -20,7 +20,7 @@
 //
 // Bit-for-bit agreement of the two builds is a property of this file, as it is for ionode_lm.hpp and ionode_cmaes.hpp: the units are
 // compiled with -ffp-contract=off -fno-fast-math (host and device pass), fp64 + - * / and sqrt are correctly rounded on both, every sum
-// has ONE written order, the only transcendentals are lm_exp and cm_log, and the generator is the CMA-ES step's (ionode_cmaes.hpp:
+// has ONE written order, the only transcendentals are lm_exp and cm_log, and the generator is the CMA-ES step's (ionode_step_math.hpp:
 // cm_philox, cm_uniform, cm_ppnd16), unchanged.  A failed factorisation is never stored (a NaN's sign is not the same everywhere).
 //
 // Execution model: ionode_lm.hpp's.  One lane per chain, N (the number of coordinates) a template argument -- every loop unrolls with
@@ -29,7 +29,7 @@
 // no atomics: a chain's result cannot depend on what shares its wavefront or its launch.
 #pragma once
 
-#include "ionode_cmaes.hpp"
+#include "ionode_step_math.hpp"
 
 namespace ionode {
 

@@ -47,6 +47,34 @@ def shard_bounds_by_cost(cost, world):
     return [(cuts[r], cuts[r + 1]) for r in range(world)]
 
 
+def population_shards(n, cost, group=None, noun="candidates"):
+    """(rank, world, bounds) of a population of n items cut over the group's ranks: bounds [(lo, hi)] * world, contiguous, of equal
+    count or -- with cost [n] -- of equal predicted cost (shard_bounds_by_cost).  (0, 1, [(0, n)]) outside torch.distributed."""
+    import torch.distributed as dist
+    on = dist.is_available() and dist.is_initialized()
+    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
+    if cost is not None and len(cost) != n:
+        from .capi import IonodeError
+        raise IonodeError(f"cost has {len(cost)} entries for {n} {noun}: the shards would not cover the population")
+    bounds = [shard_bounds(n, r, world) for r in range(world)] if cost is None else shard_bounds_by_cost(cost, world)
+    return rank, world, bounds
+
+
+def all_gather_shards(out, bounds, rank, group=None):
+    """The whole population's rows from every rank's out [hi - lo, ...] (its shard bounds[rank]): one all-gather of the shards padded
+    to the largest, the padding cut away again.  World size 1: out itself."""
+    import torch.distributed as dist
+    world = len(bounds)
+    if world == 1:
+        return out
+    m = max(hi - lo for lo, hi in bounds)
+    pad = torch.full((m,) + tuple(out.shape[1:]), float("inf"), dtype=out.dtype, device=out.device)
+    pad[: bounds[rank][1] - bounds[rank][0]] = out
+    parts = [torch.empty_like(pad) for _ in range(world)]
+    dist.all_gather(parts, pad, group=group)
+    return torch.cat([parts[r][: hi - lo] for r, (lo, hi) in enumerate(bounds)])
+
+
 def init_process_group(backend=None, device=None):
     """One process per GPU; nccl (= RCCL) when a HIP device is given, gloo otherwise.  No-op for world size 1."""
     import torch.distributed as dist

@@ -20,12 +20,10 @@ Out of scope: the NN models (their tangent sweep is refused) and CMA-ES -- both 
 sensitivities with respect to y0.  A noise model (the fit minimises the plain sum of squares) and the posterior around a fit
 are mcmc.py: adaptive Metropolis, objective.population_mcmc.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, steploop
 
 FLAG_TEXT = capi.LM_FLAG_TEXT
 
@@ -38,15 +36,7 @@ def lm_desc(n_cand, n_prot, n_params, free, base_params, *, log_parameters, lo, 
     d = capi.IonodeLmDesc(n_cand=int(n_cand), n_active=int(n_cand), n_prot=int(n_prot), n_params=int(n_params), n_free=nf,
                           log_parameters=int(bool(log_parameters)), max_iter=int(max_iter), gtol=float(gtol), xtol=float(xtol),
                           ftol=float(ftol), rho_accept=float(rho_accept), lam_max=float(lam_max))
-    none_lo = np.finfo(np.float64).tiny if log_parameters else -np.inf
-    lo = np.full(nf, none_lo) if lo is None else np.asarray(lo, dtype=np.float64).reshape(-1)
-    hi = np.full(nf, np.inf) if hi is None else np.asarray(hi, dtype=np.float64).reshape(-1)
-    base = np.asarray(base_params, dtype=np.float64).reshape(-1)
-    for j in range(min(nf, capi.LM_MAX_FREE)):
-        d.free_idx[j], d.lo[j], d.hi[j] = int(free[j]), float(lo[j]), float(hi[j])
-    for i in range(min(base.size, capi.LM_MAX_FREE)):
-        d.base[i] = float(base[i])
-    return d
+    return steploop.fill_box(d, free, base_params, lo, hi)
 
 
 def lm_init(x0, desc, lam_init):
@@ -60,9 +50,7 @@ def lm_init(x0, desc, lam_init):
     with np.errstate(all="ignore"):
         u0 = np.log(x0) if desc.log_parameters else x0
     v["u"][:], v["ut"][:], v["x"][:], v["xt"][:] = u0, u0, x0, x0
-    params = np.tile(np.array(desc.base[:desc.n_params]), (n, 1))
-    params[:, list(desc.free_idx[:nf])] = x0
-    return state, np.zeros(n, dtype=np.int32), np.zeros((n, 2), dtype=np.int32), np.repeat(params, desc.n_prot, axis=0)
+    return state, np.zeros(n, dtype=np.int32), np.zeros((n, 2), dtype=np.int32), steploop.trial_rows(desc, x0, desc.n_prot)
 
 
 def lm_step(desc, active, sse, jtr, jtj, status, state, flag, iters, trial):
@@ -76,18 +64,7 @@ def lm_step(desc, active, sse, jtr, jtj, status, state, flag, iters, trial):
             ("status", status, torch.int32, (rows,)), ("state", state, torch.float64, (desc.n_cand, capi.lm_state_doubles(nf))),
             ("flag", flag, torch.int32, (desc.n_cand,)), ("iters", iters, torch.int32, (desc.n_cand, 2)),
             ("trial", trial, torch.float64, (rows, npar))) + ((("active", active, torch.int32, (n_active,)),) if active is not None else ())
-    dev = state.device
-    for name, t, dtype, shape in want:
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise capi.IonodeError(f"lm_step: {name}: expected a contiguous {dtype} tensor {shape} on {dev}")
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
-    args = (C.byref(desc), ptr(active), ptr(sse), ptr(jtr), ptr(jtj), ptr(status), ptr(state), ptr(flag), ptr(iters), ptr(trial))
-    if dev.type == "cuda":
-        rc = capi.lib().ionode_lm_step(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    else:
-        rc = capi.lib().ionode_lm_step_host(*args)
-    if rc != 0:
-        raise capi.IonodeError(f"ionode_lm_step failed ({rc}): {capi.lib().ionode_grad_last_error().decode()}")
+    steploop.step_call("lm", desc, state.device, want, (active, sse, jtr, jtj, status, state, flag, iters, trial))
 
 
 def levenberg_marquardt(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds=None,
@@ -126,14 +103,9 @@ def levenberg_marquardt(model, x0, protocols_v, data_i, t_eval, *, base_params, 
     desc = lm_desc(max(n, 1), P, npar, free, base, log_parameters=log_parameters, lo=lo, hi=hi, max_iter=max_iter, gtol=gtol, xtol=xtol,
                    ftol=ftol)
     if n == 0:
-        return (torch.zeros((0, nf), dtype=torch.float64, device=dev), torch.zeros((0,), dtype=torch.float64, device=dev),
-                torch.zeros((0,), dtype=torch.int32, device=dev), torch.zeros((0, 2), dtype=torch.int32, device=dev))
+        return steploop.empty_result((nf,), dev)
     state, flag, iters, trial = (torch.from_numpy(a).to(dev) for a in lm_init(x0, desc, lam_init))
-    pv = torch.as_tensor(np.asarray(protocols_v), dtype=torch.float64, device=dev).contiguous()
-    te = torch.as_tensor(np.asarray(t_eval), dtype=torch.float64, device=dev).contiguous()
-    ref = torch.as_tensor(np.asarray(data_i), dtype=torch.float64, device=dev).contiguous()
-    pot = torch.from_numpy(np.tile(np.arange(P, dtype=np.int32), n)).to(dev)          # trajectory = slot * P + protocol
-    y0t = torch.tensor([list(y0)], dtype=state_dtype, device=dev).expand(n * P, D).contiguous()
+    pv, te, ref, pot, y0t = steploop.problem_tensors(protocols_v, t_eval, data_i, y0, n * P, state_dtype, dev)
     active, n_act = None, n
     every = int(compact_every or 0)
     for it in range(int(max_iter)):
@@ -146,12 +118,9 @@ def levenberg_marquardt(model, x0, protocols_v, data_i, t_eval, *, base_params, 
         if callback is not None:
             callback(it, state, flag, iters)
         if every and (it + 1) % every == 0:   # the one read: who is still running
-            slots = torch.arange(n, device=dev) if active is None else active.long()
-            keep = torch.nonzero(flag[slots] == capi.LM_RUNNING).reshape(-1)       # positions among the current slots, ascending
-            if keep.numel() == 0:
+            left = steploop.compact(flag, active, n_act, trial, capi.LM_RUNNING)
+            if left is None:
                 break
-            if keep.numel() < n_act:
-                trial = trial.reshape(n_act, P * npar)[keep].reshape(-1, npar).contiguous()
-                active, n_act = slots[keep].to(torch.int32).contiguous(), int(keep.numel())
+            active, n_act, trial = left
     v = capi.lm_state_views(state, nf)
     return v["x"].contiguous(), v["f"].contiguous(), flag, iters

@@ -25,12 +25,10 @@ kernel bit for bit.
 Out of scope: other samplers (DE-MC, DREAM, HMC on the existing gradients, tempering), a Laplace likelihood on the "sae" sums, priors
 other than the box, per-protocol or per-sample noise, sampling MLP weights, bit-compatibility with PINTS, diagnostics beyond R-hat.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, steploop
 
 FLAG_TEXT = capi.MCMC_FLAG_TEXT
 
@@ -52,13 +50,7 @@ def mcmc_desc(n_chain, n_prot, n_params, free, base_params, *, log_parameters, l
         d.sigma_lo, d.sigma_hi = float(sigma_bounds[0]), float(sigma_bounds[1])
     else:
         d.sigma = float(sigma)
-    lo, hi = (np.asarray(b, dtype=np.float64).reshape(-1) for b in (lo, hi))
-    base = np.asarray(base_params, dtype=np.float64).reshape(-1)
-    for j in range(min(nf, capi.LM_MAX_FREE)):
-        d.free_idx[j], d.lo[j], d.hi[j] = int(free[j]), float(lo[j]), float(hi[j])
-    for i in range(min(base.size, capi.LM_MAX_FREE)):
-        d.base[i] = float(base[i])
-    return d
+    return steploop.fill_box(d, free, base_params, lo, hi)
 
 
 def mcmc_init(x0, desc, scale=None):
@@ -89,10 +81,8 @@ def mcmc_init(x0, desc, scale=None):
             u0[:, nf] = np.log(x0[:, nf])
     v["u"][:], v["ut"][:], v["mu"][:], v["x"][:], v["xt"][:] = u0, u0, u0, x0, x0
     v["C"][:] = np.diag(s * s)
-    params = np.tile(np.array(desc.base[:desc.n_params]), (K, 1))
-    params[:, list(desc.free_idx[:nf])] = x0[:, :nf]
     samples = np.full((K, max(int(desc.sample_cap), 0), n + 1), np.nan)
-    return state, np.zeros(K, dtype=np.int32), np.zeros((K, 2), dtype=np.int32), np.repeat(params, desc.n_prot, axis=0), samples
+    return state, np.zeros(K, dtype=np.int32), np.zeros((K, 2), dtype=np.int32), steploop.trial_rows(desc, x0, desc.n_prot), samples
 
 
 def mcmc_step(desc, active, value, status, state, flag, iters, trial, samples=None):
@@ -109,18 +99,7 @@ def mcmc_step(desc, active, value, status, state, flag, iters, trial, samples=No
             ("iters", iters, torch.int32, (desc.n_chain, 2)), ("trial", trial, torch.float64, (rows, npar))) \
         + ((("active", active, torch.int32, (n_active,)),) if active is not None else ()) \
         + ((("samples", samples, torch.float64, (desc.n_chain, desc.sample_cap, n + 1)),) if samples is not None else ())
-    dev = state.device
-    for name, t, dtype, shape in want:
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise capi.IonodeError(f"mcmc_step: {name}: expected a contiguous {dtype} tensor {shape} on {dev}")
-    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
-    args = (C.byref(desc), ptr(active), ptr(value), ptr(status), ptr(state), ptr(flag), ptr(iters), ptr(trial), ptr(samples))
-    if dev.type == "cuda":
-        rc = capi.lib().ionode_mcmc_step(*args, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    else:
-        rc = capi.lib().ionode_mcmc_step_host(*args)
-    if rc != 0:
-        raise capi.IonodeError(f"ionode_mcmc_step failed ({rc}): {capi.lib().ionode_grad_last_error().decode()}")
+    steploop.step_call("mcmc", desc, state.device, want, (active, value, status, state, flag, iters, trial, samples))
 
 
 def sample(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds, sigma=None,
@@ -177,16 +156,10 @@ def sample(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2
                      max_iter=max_iter, sigma=sigma, sigma_bounds=sigma_bounds, adapt_start=adapt_start, thin=thin, eta=eta,
                      target_accept=target_accept, epsilon=epsilon, seed=seed, chain_base=chain_offset)
     if K == 0:
-        return (torch.zeros((0, desc.sample_cap, n + 1), dtype=torch.float64, device=dev), torch.zeros((0,), dtype=torch.float64, device=dev),
-                torch.zeros((0,), dtype=torch.int32, device=dev), torch.zeros((0, 2), dtype=torch.int32, device=dev))
+        return steploop.empty_result((desc.sample_cap, n + 1), dev)
     state, flag, iters, trial, samples = (torch.from_numpy(a).to(dev) for a in mcmc_init(x0, desc, scale))
-    pv = torch.as_tensor(np.asarray(protocols_v), dtype=torch.float64, device=dev).contiguous()
-    te = torch.as_tensor(np.asarray(t_eval), dtype=torch.float64, device=dev).contiguous()
-    ref = torch.as_tensor(np.asarray(data_i), dtype=torch.float64, device=dev).contiguous()
-    pot = torch.from_numpy(np.tile(np.arange(P, dtype=np.int32), K)).to(dev)      # trajectory = slot * P + protocol
-    y0t = torch.tensor([list(y0)], dtype=state_dtype, device=dev).expand(K * P, D).contiguous()
+    pv, te, ref, pot, y0t = steploop.problem_tensors(protocols_v, t_eval, data_i, y0, K * P, state_dtype, dev)
     mlp = {} if weights is None else dict(weights=weights, mlp_layers=mlp_layers, mlp_width=mlp_width, weights_key=weights_key)
-    own = torch.arange(K, dtype=torch.int32, device=dev)
     active, n_act = None, K
     every = int(compact_every or 0)
     for it in range(int(max_iter) + 1):
@@ -198,13 +171,10 @@ def sample(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2
         if callback is not None:
             callback(it, state, flag, iters)
         if every and it % every == 0 and it and it < int(max_iter):   # the one read: who is still running
-            slots = own if active is None else active
-            keep = torch.nonzero(flag[slots.long()] == capi.MCMC_RUNNING).reshape(-1)   # positions among the current slots, ascending
-            if keep.numel() == 0:
+            left = steploop.compact(flag, active, n_act, trial, capi.MCMC_RUNNING)
+            if left is None:
                 break
-            if keep.numel() < n_act:
-                trial = trial.reshape(n_act, P * npar)[keep].reshape(-1, npar).contiguous()
-                active, n_act = slots[keep].to(torch.int32).contiguous(), int(keep.numel())
+            active, n_act, trial = left
     rate = iters[:, 1].double() / iters[:, 0].clamp(min=1).double()
     return samples, rate, flag, iters
 

@@ -14,6 +14,36 @@ import torch
 from . import batched, capi, distributed, grad
 
 
+def _auto_max_step(max_step, model, rows, protocols_v):
+    """max_step as a number: "auto" is resolved ONCE, before sharding, to grad.stable_step_cap over rows() [*, NPAR] -- the parameter
+    rows the caller caps over: every candidate, or the stiffest corner of the box (_corner_or_starts) -- so that the function being
+    evaluated is the same on every rank and in every iteration.  Non-finite rows are left out (they fail either way and must not void
+    everyone's cap); 0.0 (no cap) when none remains, and for the NN models, which carry no such cap."""
+    if not isinstance(max_step, str):
+        return max_step
+    if max_step != "auto":
+        raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
+    if model in (capi.MODEL_NNF, capi.MODEL_NND):
+        return 0.0
+    rows = rows()
+    fin = np.isfinite(rows).all(axis=1)
+    if not fin.any():
+        return 0.0
+    return grad.stable_step_cap(model, torch.from_numpy(rows[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64)))
+
+
+def _corner_or_starts(base, free, bounds, starts):
+    """The rows a fit's "auto" step cap is taken over: the upper corner of the box -- the stiffest point the fit can visit -- when the
+    upper bounds are finite, else the starting population."""
+    rows = np.tile(base, (starts.shape[0], 1))
+    if bounds is not None and np.isfinite(np.asarray(bounds[1], dtype=np.float64)).all():
+        rows = rows[:1]
+        rows[:, free] = np.asarray(bounds[1], dtype=np.float64)
+    else:
+        rows[:, free] = starts
+    return rows
+
+
 def population_sum_of_squares(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), prot_t0=0.0,
                               prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
                               max_total_steps=1_000_000, group=None, device=None, solver=None, fused=True, cost=None,
@@ -67,15 +97,9 @@ def _population_error(kind, per_protocol, candidates, protocols_v, data_i, t_eva
                       mlp_width, weights_key):
     """The one body of population_sum_of_squares (kind "sse": [C] sums) and population_mean_abs_error (kind "sae": [C] means, or
     [C, P] per-protocol means): shard the candidates, solve, reduce each candidate's P sweeps, all-gather."""
-    import torch.distributed as dist
     cand = np.asarray(candidates, dtype=np.float64)
     C, P = cand.shape[0], np.asarray(protocols_v).shape[0]
-    on = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
-    if cost is not None and len(cost) != C:
-        raise capi.IonodeError(f"cost has {len(cost)} entries for {C} candidates: the shards would not cover the population")
-    bounds = [distributed.shard_bounds(C, r, world) for r in range(world)] if cost is None \
-        else distributed.shard_bounds_by_cost(cost, world)
+    rank, world, bounds = distributed.population_shards(C, cost, group, "candidates")
     lo, hi = bounds[rank]
     dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
     solve = batched.solve if solver is None else solver
@@ -118,15 +142,7 @@ def _population_error(kind, per_protocol, candidates, protocols_v, data_i, t_eva
             err = per / Nt if per_protocol else per.sum(dim=1) / (P * Nt)
         ok = (sol.status.reshape(hi - lo, S)[:, :P] == 0).all(dim=1)
         out = torch.where(ok[:, None] if per_protocol else ok, err, torch.full_like(err, float("inf")))
-    if world == 1:
-        return out
-    # all-gather of unequal shards: pad to the largest shard
-    m = max(b[1] - b[0] for b in bounds)
-    pad = torch.full((m,) + cols, float("inf"), dtype=torch.float64, device=dev)
-    pad[: hi - lo] = out
-    parts = [torch.empty_like(pad) for _ in range(world)]
-    dist.all_gather(parts, pad, group=group)
-    return torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
+    return distributed.all_gather_shards(out, bounds, rank, group)   # (unequal shards: padded to the largest)
 
 
 def population_sum_of_squares_s1(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), prot_t0=0.0,
@@ -179,7 +195,6 @@ def _population_error_s1(kind, candidates, protocols_v, data_i, t_eval, *, base_
     """The one body of population_sum_of_squares_s1 (kind "sse": [C] sums) and population_mean_abs_error_s1 (kind "sae": [C] means),
     each with its gradient: the population-wide step cap, shard, fused solve and sweep, reduce each candidate's P sweeps, all-gather."""
     who = "population_sum_of_squares_s1" if kind == "sse" else "population_mean_abs_error_s1"
-    import torch.distributed as dist
     if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
         raise capi.IonodeError(f"{who}: HH 2-state and 6-state models only")
     D, npar = (6, 12) if model == capi.MODEL_MARKOV6 else (2, 8)
@@ -189,23 +204,13 @@ def _population_error_s1(kind, candidates, protocols_v, data_i, t_eval, *, base_
     base = np.asarray(base_params, dtype=np.float64)
     if base.shape != (npar,) or len(y0) != D:
         raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
-    on = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
-    if cost is not None and len(cost) != C:
-        raise capi.IonodeError(f"cost has {len(cost)} entries for {C} candidates: the shards would not cover the population")
-    bounds = [distributed.shard_bounds(C, r, world) for r in range(world)] if cost is None \
-        else distributed.shard_bounds_by_cost(cost, world)
+    rank, world, bounds = distributed.population_shards(C, cost, group, "candidates")
     lo, hi = bounds[rank]
     dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
     solve = (grad.sum_of_squares if kind == "sse" else grad.sum_of_abs) if solver is None else solver
     params_all = np.tile(base, (C, 1))
     params_all[:, free] = cand
-    if isinstance(max_step, str):
-        if max_step != "auto":
-            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
-        fin = np.isfinite(params_all).all(axis=1)   # (a non-finite candidate fails either way; it must not void everyone's cap)
-        max_step = grad.stable_step_cap(model, torch.from_numpy(params_all[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
-            if fin.any() else 0.0
+    max_step = _auto_max_step(max_step, model, lambda: params_all, protocols_v)
     nf = len(free)
     out = torch.empty((hi - lo, 1 + nf), dtype=torch.float64, device=dev)
     if hi > lo:
@@ -227,14 +232,7 @@ def _population_error_s1(kind, candidates, protocols_v, data_i, t_eval, *, base_
             err, gc = err / n_samples, gc / n_samples
         out[:, 0] = torch.where(ok, err, torch.full_like(err, float("inf")))
         out[:, 1:] = torch.where(ok[:, None], gc, torch.zeros_like(gc))
-    if world > 1:
-        m = max(b[1] - b[0] for b in bounds)
-        pad = torch.zeros((m, 1 + nf), dtype=torch.float64, device=dev)
-        pad[:, 0] = float("inf")
-        pad[: hi - lo] = out
-        parts = [torch.empty_like(pad) for _ in range(world)]
-        dist.all_gather(parts, pad, group=group)
-        out = torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
+    out = distributed.all_gather_shards(out, bounds, rank, group)
     return out[:, 0].contiguous(), out[:, 1:].contiguous()
 
 
@@ -257,7 +255,6 @@ def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_par
     docstring).
     """
     who = "population_gauss_newton"
-    import torch.distributed as dist
     from . import sensitivity
     if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
         raise capi.IonodeError(f"{who}: HH 2-state and 6-state models only")
@@ -268,23 +265,13 @@ def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_par
     base = np.asarray(base_params, dtype=np.float64)
     if base.shape != (npar,) or len(y0) != D:
         raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
-    on = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
-    if cost is not None and len(cost) != C:
-        raise capi.IonodeError(f"cost has {len(cost)} entries for {C} candidates: the shards would not cover the population")
-    bounds = [distributed.shard_bounds(C, r, world) for r in range(world)] if cost is None \
-        else distributed.shard_bounds_by_cost(cost, world)
+    rank, world, bounds = distributed.population_shards(C, cost, group, "candidates")
     lo, hi = bounds[rank]
     dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
     solve = sensitivity.gauss_newton if solver is None else solver
     params_all = np.tile(base, (C, 1))
     params_all[:, free] = cand
-    if isinstance(max_step, str):
-        if max_step != "auto":
-            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
-        fin = np.isfinite(params_all).all(axis=1)   # (a non-finite candidate fails either way; it must not void everyone's cap)
-        max_step = grad.stable_step_cap(model, torch.from_numpy(params_all[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
-            if fin.any() else 0.0
+    max_step = _auto_max_step(max_step, model, lambda: params_all, protocols_v)
     nf = len(free)
     out = torch.empty((hi - lo, 1 + nf + nf * nf), dtype=torch.float64, device=dev)
     if hi > lo:
@@ -307,14 +294,7 @@ def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_par
         out[:, 0] = torch.where(ok, err, torch.full_like(err, float("inf")))
         out[:, 1:1 + nf] = torch.where(ok[:, None], g, torch.zeros_like(g))
         out[:, 1 + nf:] = torch.where(ok[:, None], H.reshape(n, nf * nf), torch.zeros((), dtype=torch.float64, device=dev))
-    if world > 1:
-        m = max(b[1] - b[0] for b in bounds)
-        pad = torch.zeros((m, out.shape[1]), dtype=torch.float64, device=dev)
-        pad[:, 0] = float("inf")
-        pad[: hi - lo] = out
-        parts = [torch.empty_like(pad) for _ in range(world)]
-        dist.all_gather(parts, pad, group=group)
-        out = torch.cat([parts[r][: bounds[r][1] - bounds[r][0]] for r in range(world)])
+    out = distributed.all_gather_shards(out, bounds, rank, group)
     return out[:, 0].contiguous(), out[:, 1:1 + nf].contiguous(), out[:, 1 + nf:].reshape(-1, nf, nf).contiguous()
 
 
@@ -343,7 +323,6 @@ def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free
     respect to y0.  A noise model and the posterior around a fit are population_mcmc / mcmc.py.
     """
     who = "population_fit"
-    import torch.distributed as dist
     from . import fit
     if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
         raise capi.IonodeError(f"{who}: HH 2-state and 6-state models only")
@@ -355,26 +334,10 @@ def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free
     base = np.asarray(base_params, dtype=np.float64)
     if base.shape != (npar,) or len(y0) != D:
         raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
-    on = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
-    if cost is not None and len(cost) != C:
-        raise capi.IonodeError(f"cost has {len(cost)} entries for {C} candidates: the shards would not cover the population")
-    bounds_r = [distributed.shard_bounds(C, r, world) for r in range(world)] if cost is None \
-        else distributed.shard_bounds_by_cost(cost, world)
+    rank, world, bounds_r = distributed.population_shards(C, cost, group, "candidates")
     lo, hi = bounds_r[rank]
     dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
-    if isinstance(max_step, str):
-        if max_step != "auto":
-            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
-        corner = np.tile(base, (C, 1))
-        if bounds is not None and np.isfinite(np.asarray(bounds[1], dtype=np.float64)).all():
-            corner = corner[:1]
-            corner[:, free] = np.asarray(bounds[1], dtype=np.float64)
-        else:
-            corner[:, free] = cand
-        fin = np.isfinite(corner).all(axis=1)   # (a non-finite start fails either way; it must not void everyone's cap)
-        max_step = grad.stable_step_cap(model, torch.from_numpy(corner[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
-            if fin.any() else 0.0
+    max_step = _auto_max_step(max_step, model, lambda: _corner_or_starts(base, free, bounds, cand), protocols_v)
     x, sse, flag, iters = fit.levenberg_marquardt(model, cand[lo:hi], protocols_v, data_i, t_eval, base_params=base, free=free,
                                                   log_parameters=log_parameters, bounds=bounds, prot_t0=prot_t0, prot_dt=prot_dt, y0=y0,
                                                   state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e, obs_open_state_only=obs_open_state_only,
@@ -382,13 +345,7 @@ def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free
                                                   solver=solver, max_iter=max_iter, gtol=gtol, xtol=xtol, ftol=ftol, lam_init=lam_init,
                                                   compact_every=compact_every)
     out = torch.cat([x, sse[:, None], flag.double()[:, None], iters.double()], dim=1)   # [n, nf + 4]
-    if world > 1:
-        m = max(b[1] - b[0] for b in bounds_r)
-        pad = torch.zeros((m, nf + 4), dtype=torch.float64, device=dev)
-        pad[: hi - lo] = out
-        parts = [torch.empty_like(pad) for _ in range(world)]
-        dist.all_gather(parts, pad, group=group)
-        out = torch.cat([parts[r][: bounds_r[r][1] - bounds_r[r][0]] for r in range(world)])
+    out = distributed.all_gather_shards(out, bounds_r, rank, group)
     return out[:, :nf].contiguous(), out[:, nf].contiguous(), out[:, nf + 1].to(torch.int32), out[:, nf + 2:].to(torch.int32).contiguous()
 
 
@@ -416,7 +373,6 @@ def population_cmaes(starts, protocols_v, data_i, t_eval, *, base_params, free=(
     errors are.  A run's result does not depend on the shard it ran in.  `solver` (tests only): a stand-in with batched.solve's
     signature on CPU tensors; the step then runs as ionode_cmaes_step_host.
     """
-    import torch.distributed as dist
     from . import cmaes
     D, npar = capi.n_state(model), capi.n_params(model)
     free = [int(f) for f in free]
@@ -426,29 +382,10 @@ def population_cmaes(starts, protocols_v, data_i, t_eval, *, base_params, free=(
     base = np.asarray(base_params, dtype=np.float64)
     if base.shape != (npar,) or len(y0) != D:
         raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
-    on = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
-    if cost is not None and len(cost) != K:
-        raise capi.IonodeError(f"cost has {len(cost)} entries for {K} runs: the shards would not cover the population")
-    bounds_r = [distributed.shard_bounds(K, r, world) for r in range(world)] if cost is None \
-        else distributed.shard_bounds_by_cost(cost, world)
+    rank, world, bounds_r = distributed.population_shards(K, cost, group, "runs")
     lo, hi = bounds_r[rank]
     dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
-    if isinstance(max_step, str):
-        if max_step != "auto":
-            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
-        if model in (capi.MODEL_NNF, capi.MODEL_NND):
-            max_step = 0.0
-        else:
-            corner = np.tile(base, (K, 1))
-            if bounds is not None and np.isfinite(np.asarray(bounds[1], dtype=np.float64)).all():
-                corner = corner[:1]
-                corner[:, free] = np.asarray(bounds[1], dtype=np.float64)
-            else:
-                corner[:, free] = cand
-            fin = np.isfinite(corner).all(axis=1)
-            max_step = grad.stable_step_cap(model, torch.from_numpy(corner[fin]), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
-                if fin.any() else 0.0
+    max_step = _auto_max_step(max_step, model, lambda: _corner_or_starts(base, free, bounds, cand), protocols_v)
     x, val, flag, iters = cmaes.minimise(model, cand[lo:hi], protocols_v, data_i, t_eval, base_params=base, free=free, log_parameters=log_parameters,
                                          bounds=bounds, objective=objective, popsize=popsize, sigma0=sigma0, scale=scale, seed=seed,
                                          max_iter=max_iter, unchanged_iters=unchanged_iters, unchanged_threshold=unchanged_threshold, tolx=tolx,
@@ -457,13 +394,7 @@ def population_cmaes(starts, protocols_v, data_i, t_eval, *, base_params, free=(
                                          obs_e=obs_e, obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps,
                                          max_step=float(max_step), rtol=rtol, atol=atol, device=dev, solver=solver, run_offset=lo)
     out = torch.cat([x, val[:, None], flag.double()[:, None], iters.double()], dim=1)   # [n, nf + 4]
-    if world > 1:
-        m = max(b[1] - b[0] for b in bounds_r)
-        pad = torch.full((m, nf + 4), float("inf"), dtype=torch.float64, device=dev)
-        pad[: hi - lo] = out
-        parts = [torch.empty_like(pad) for _ in range(world)]
-        dist.all_gather(parts, pad, group=group)
-        out = torch.cat([parts[r][: bounds_r[r][1] - bounds_r[r][0]] for r in range(world)])
+    out = distributed.all_gather_shards(out, bounds_r, rank, group)
     return out[:, :nf].contiguous(), out[:, nf].contiguous(), out[:, nf + 1].to(torch.int32), out[:, nf + 2:].to(torch.int32).contiguous()
 
 
@@ -490,7 +421,6 @@ def population_mcmc(starts, protocols_v, data_i, t_eval, *, base_params, free=(0
     the shard it ran in.  `solver` (tests only): a stand-in with batched.solve's signature on CPU tensors; the step then runs as
     ionode_mcmc_step_host.
     """
-    import torch.distributed as dist
     from . import mcmc
     D, npar = capi.n_state(model), capi.n_params(model)
     free = [int(f) for f in free]
@@ -507,24 +437,14 @@ def population_mcmc(starts, protocols_v, data_i, t_eval, *, base_params, free=(0
         raise capi.IonodeError("population_mcmc: bounds = (lo, hi) are required: the box is the prior")
     if (sigma is None) == (sigma_bounds is None):
         raise capi.IonodeError("population_mcmc: exactly one of sigma (fixed noise) and sigma_bounds (sampled noise) must be given")
-    on = dist.is_available() and dist.is_initialized()
-    rank, world = (dist.get_rank(group), dist.get_world_size(group)) if on else (0, 1)
-    if cost is not None and len(cost) != K:
-        raise capi.IonodeError(f"cost has {len(cost)} entries for {K} chains: the shards would not cover the population")
-    bounds_r = [distributed.shard_bounds(K, r, world) for r in range(world)] if cost is None \
-        else distributed.shard_bounds_by_cost(cost, world)
+    rank, world, bounds_r = distributed.population_shards(K, cost, group, "chains")
     lo, hi = bounds_r[rank]
     dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
-    if isinstance(max_step, str):
-        if max_step != "auto":
-            raise capi.IonodeError("max_step must be a number (ms) or 'auto'")
-        if model in (capi.MODEL_NNF, capi.MODEL_NND):
-            max_step = 0.0
-        else:
-            corner = base[None].copy()
-            corner[:, free] = np.asarray(bounds[1], dtype=np.float64)
-            max_step = grad.stable_step_cap(model, torch.from_numpy(corner), torch.as_tensor(np.asarray(protocols_v, dtype=np.float64))) \
-                if np.isfinite(corner).all() else 0.0
+    def corner():
+        rows = base[None].copy()
+        rows[:, free] = np.asarray(bounds[1], dtype=np.float64)
+        return rows
+    max_step = _auto_max_step(max_step, model, corner, protocols_v)
     smp, rate, flag, iters = mcmc.sample(model, cand[lo:hi], protocols_v, data_i, t_eval, base_params=base, free=free, log_parameters=log_parameters,
                                          bounds=bounds, sigma=sigma, sigma_bounds=sigma_bounds, scale=scale, seed=seed, max_iter=max_iter,
                                          adapt_start=adapt_start, thin=thin, eta=eta, target_accept=target_accept, epsilon=epsilon,
@@ -534,13 +454,7 @@ def population_mcmc(starts, protocols_v, data_i, t_eval, *, base_params, free=(0
                                          max_step=float(max_step), rtol=rtol, atol=atol, device=dev, solver=solver, chain_offset=lo)
     R = smp.shape[1]
     out = torch.cat([smp.reshape(hi - lo, R * (n + 1)), rate[:, None], flag.double()[:, None], iters.double()], dim=1)   # [chains, R (n + 1) + 4]
-    if world > 1:
-        m = max(b[1] - b[0] for b in bounds_r)
-        pad = torch.full((m, R * (n + 1) + 4), float("inf"), dtype=torch.float64, device=dev)
-        pad[: hi - lo] = out
-        parts = [torch.empty_like(pad) for _ in range(world)]
-        dist.all_gather(parts, pad, group=group)
-        out = torch.cat([parts[r][: bounds_r[r][1] - bounds_r[r][0]] for r in range(world)])
+    out = distributed.all_gather_shards(out, bounds_r, rank, group)
     w = R * (n + 1)
     return (out[:, :w].reshape(-1, R, n + 1).contiguous(), out[:, w].contiguous(), out[:, w + 1].to(torch.int32),
             out[:, w + 2:].to(torch.int32).contiguous())
