@@ -803,6 +803,110 @@ int ionode_mcmc_step(const ionode_mcmc_desc *d, const int32_t *active, const dou
 int ionode_mcmc_step_host(const ionode_mcmc_desc *d, const int32_t *active, const double *value, const int32_t *status, double *state,
                           int32_t *flag, int32_t *iters, double *trial, double *samples);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Manifold MALA step for many independent chains (closed-form models; new symbols, ABI stays 10).
+ * The adaptive-Metropolis step above learns the posterior's shape from its own history.  Under the Gaussian noise model it
+ * samples, J^T J / sigma^2 -- the Gauss-Newton matrix the tangent sweep sums for the Levenberg-Marquardt step -- is the expected
+ * Fisher information: the local metric of the posterior, at every point, from iteration 0.  This step is the "simplified manifold
+ * MALA" of Girolami and Calderhead (2011): a Metropolis-adjusted Langevin proposal preconditioned by that metric.  An iteration
+ * of all chains is the Levenberg-Marquardt step's evaluation (the checkpointed forward with the fused sum of squares, then the
+ * tangent sweep's jtr / jtj) of the trial tensor [n_active * P][NPAR], then the entry point below: the TELL of that evaluation,
+ * then the PROPOSAL of the next, which overwrites the trial tensor in place.  No host synchronisation in between.
+ *
+ * Launch slot s holds chain active[s] (active == NULL: chain s).  sse / jtr / jtj / status (laid out as ionode_lm_step takes them)
+ * and trial are indexed by slot -- the slot's P trajectories are rows s P .. s P + P - 1, one per protocol -- and state / flag /
+ * iters / samples (laid out as ionode_mcmc_step takes them) by chain.
+ *
+ * Coordinates, target and prior are the adaptive-Metropolis step's: u_j = log x_j (log_parameters) or x_j for the n_free free
+ * parameters and, with sample_sigma, u_sigma = log sigma as the last; n = n_free + sample_sigma <= IONODE_MCMC_MAX_DIM;
+ * lp = -N u_sigma - (S / 2) exp(-2 u_sigma), S = sum_p sse over p = 0 .. P - 1 in that order (a non-zero status on any of the P
+ * rows, or a NaN, makes S = +inf), N = n_samples; the prior is uniform over the finite box in the search space.
+ * One call, for every slot whose chain is running (flag 0), at the chain's iteration t = iters[chain][0], in this order:
+ *   metric   at the evaluated point (x, sigma) -- the start at t = 0, else the proposal: g_x = sum_p jtr, H_x = sum_p jtj over the
+ *            free rows and columns, p in order (only the lower triangle of jtj is read); log_parameters: g_j x_j and H_jl (x_j x_l);
+ *            grad_j = -g_j / sigma^2, G_jl = H_jl / sigma^2 (1 / sigma^2 = exp(-2 u_sigma), the library's exp); with sample_sigma
+ *            grad_s = -N + S / sigma^2, G_ss = 2 N and zero cross terms: the expected information.  Then the ridge, a function of
+ *            the point alone: G_jj += ridge max(G_jj, IONODE_LM_FLOOR_REL max_l G_ll, IONODE_LM_FLOOR_ABS), the Levenberg-Marquardt
+ *            step's diagonal.  G = L_t L_t^T by Cholesky, lower triangle packed by rows, ld_t = sum_j log L_jj (the library's log).
+ *            The metric "does not factor" when a pivot is not a positive finite number or an entry of grad or ld_t is not finite.
+ *   t = 0    the evaluation is the start's: lp becomes its log-posterior.  IONODE_MALA_NONFINITE if the start is outside the box
+ *            or lp is not finite; else IONODE_MALA_DEGENERATE if the metric does not factor; else (grad, L, ld) become its.
+ *   tell     t >= 1, with eps = exp(log_eps) as the state holds it (the step size the proposal was drawn with): alpha = 0 if the
+ *            proposal was outside the box (IONODE_MALA_STATE_OUTSIDE), lp_t is not finite or the metric does not factor.
+ *            Otherwise y = L_t^-1 grad_t, d = L_t^-T y, mu_t = ut + (eps^2 / 2) d, v = L_t^T (u - mu_t),
+ *            lq_r = (ld_t - n log_eps) - (v . v) / (2 eps^2), ratio = ((lp_t + lq_r) - lp) - lq_f with lq_f as the proposing call
+ *            stored it (IONODE_MALA_STATE_LQF), alpha = exp(min(ratio, 0)) (0 for a NaN ratio).  Accepted iff alpha > 0 and
+ *            log w < ratio, w the uniform below: then (u, x, lp, grad, L, ld) <- the proposal's and iters[chain][1] goes up.  A
+ *            factor that failed is never stored.
+ *   adapt    t >= 1: log_eps <- log_eps + exp(-eta log(t + 1)) (alpha - target_accept).  Nothing else adapts.
+ *   record   t % thin == 0 and t / thin < sample_cap: row t / thin of samples[chain] <- (x [n_free], sigma if sampled, lp).
+ *   stop     IONODE_MALA_NONFINITE and IONODE_MALA_DEGENERATE come from t = 0 only (a bad trial metric is a rejection, not a
+ *            stop); IONODE_MALA_MAXITER: t >= max_iter.  A chain whose flag is not 0 is frozen: a later call changes nothing of
+ *            its state, flag or iters and writes its current x into its slot's trial rows.
+ *   propose  z: n normal deviates (below); eps = exp(log_eps) after the adaptation; y = L^-1 grad, w_j = (eps^2 / 2) y_j + eps z_j,
+ *            ut = u + L^-T w, that is u + (eps^2 / 2) G^-1 grad + eps L^-T z; lq_f = (ld - n log_eps) - (z . z) / 2.  A ut outside
+ *            the box (or not a number) is not redrawn: the OUTSIDE word is set and the slot's trial rows get the current x (its
+ *            evaluation is wasted, its tell rejects without using the values).  Otherwise xt = exp(ut) clamped into [lo, hi] or
+ *            xt = ut, and the P trial rows are base[] with the free columns replaced by xt.  Sigma never enters the rows.
+ *
+ * Random numbers: the CMA-ES step's generator, unchanged.  The proposal evaluated at iteration t takes its deviates from the
+ * counters (chain_base + chain, t, 0, pair): coordinates 2 pair and 2 pair + 1; the acceptance uniform of iteration t is the first
+ * uniform of (chain_base + chain, t, 1, 0).
+ *
+ * state [n_chain][IONODE_MALA_STATE_U + 5 n + n^2] fp64, per chain: [IONODE_MALA_STATE_LP] lp, [IONODE_MALA_STATE_LOG_EPS] log_eps,
+ * [IONODE_MALA_STATE_OUTSIDE] 1 if the proposal in flight left the box, else 0, [IONODE_MALA_STATE_ALPHA] the last alpha,
+ * [IONODE_MALA_STATE_LD] ld of the current point, [IONODE_MALA_STATE_LQF] lq_f of the proposal in flight; then from
+ * IONODE_MALA_STATE_U on: u, ut, x, xt, grad [n each; with sample_sigma the last entry of x and xt is sigma]; L [n][n], lower
+ * triangular, row-major.  To start a chain the caller sets log_eps = log eps0, u = ut = the start in the search space, x = xt =
+ * the start, the rest 0, flag = 0, iters = 0, and writes the start into the slot's trial rows.  iters as the adaptive-Metropolis
+ * step's.
+ *
+ * Execution model: one lane per chain, n a compile-time constant; one packed triangle live at a time (L_t through the tell, then
+ * word by word L_t or the stored L for the proposal); no scratch, no LDS, no cross-lane operation, no atomic, every sum in one
+ * written order.  The host entry point runs the same per-chain routine on host pointers, no HIP call: its results equal the
+ * kernel's bit for bit, and a chain's results do not depend on the other chains of the call or on its slot.
+ * Refusals, all before anything is touched, text in the gradient path's error string: those of ionode_mcmc_step (jtr and jtj are
+ * required buffers too), and a ridge that is negative or not finite, or n_samples that is not positive and finite.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define IONODE_MALA_STATE_LP 0
+#define IONODE_MALA_STATE_LOG_EPS 1
+#define IONODE_MALA_STATE_OUTSIDE 2
+#define IONODE_MALA_STATE_ALPHA 3
+#define IONODE_MALA_STATE_LD 4
+#define IONODE_MALA_STATE_LQF 5
+#define IONODE_MALA_STATE_U 6
+#define IONODE_MALA_RUNNING 0
+#define IONODE_MALA_MAXITER 1
+#define IONODE_MALA_DEGENERATE 2
+#define IONODE_MALA_NONFINITE 3
+
+typedef struct ionode_mala_desc {
+  int32_t n_chain;         /* K: chains the state arrays hold */
+  int32_t n_active;        /* launch slots of this call, <= n_chain */
+  int32_t n_prot;          /* P: trajectories per chain */
+  int32_t n_params;        /* NPAR: 8 (HH 2-state) or 12 (6-state) */
+  int32_t n_free;          /* nf */
+  int32_t log_parameters;
+  int32_t sample_sigma;    /* 1: log sigma is the last coordinate, within [sigma_lo, sigma_hi]; 0: sigma is fixed */
+  int32_t max_iter;        /* Metropolis-Hastings decisions a chain makes */
+  int32_t thin;            /* every thin-th iteration is recorded */
+  int32_t sample_cap;      /* rows of samples[chain] */
+  int32_t chain_base;      /* index of the state arrays' first chain among all chains of the run (sharding): the generator sees chain_base + chain */
+  int32_t reserved;
+  int64_t seed;
+  double n_samples;        /* N: residuals behind S, P times the samples of a trace */
+  double sigma, sigma_lo, sigma_hi;
+  double eta, target_accept, ridge;
+  int32_t free_idx[IONODE_LM_MAX_FREE];
+  double base[IONODE_LM_MAX_FREE];
+  double lo[IONODE_LM_MAX_FREE], hi[IONODE_LM_MAX_FREE];   /* the box, in the parameters: finite (log_parameters: lo > 0) */
+} ionode_mala_desc;
+
+int ionode_mala_step(const ionode_mala_desc *d, const int32_t *active, const double *sse, const double *jtr, const double *jtj,
+                     const int32_t *status, double *state, int32_t *flag, int32_t *iters, double *trial, double *samples, void *stream);
+int ionode_mala_step_host(const ionode_mala_desc *d, const int32_t *active, const double *sse, const double *jtr, const double *jtj,
+                          const int32_t *status, double *state, int32_t *flag, int32_t *iters, double *trial, double *samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -211,6 +211,45 @@ def mcmc_state_views(state, nf, sample_sigma):
     return v
 
 
+# the manifold-MALA step (include/ionode.h ionode_mala_desc, IONODE_MALA_*): descriptor, state layout, stop flags
+MALA_STATE_LP, MALA_STATE_LOG_EPS, MALA_STATE_OUTSIDE, MALA_STATE_ALPHA, MALA_STATE_LD, MALA_STATE_LQF, MALA_STATE_U = range(7)
+MALA_RUNNING, MALA_MAXITER, MALA_DEGENERATE, MALA_NONFINITE = range(4)
+MALA_FLAG_TEXT = {0: "running", 1: "iteration cap", 2: "the start's metric (J^T J / sigma^2 with its ridge) is not positive definite",
+                  3: "start outside the box, or its log-posterior not finite"}
+
+
+class IonodeMalaDesc(C.Structure):
+    _fields_ = [
+        ("n_chain", C.c_int32), ("n_active", C.c_int32), ("n_prot", C.c_int32), ("n_params", C.c_int32), ("n_free", C.c_int32),
+        ("log_parameters", C.c_int32), ("sample_sigma", C.c_int32), ("max_iter", C.c_int32), ("thin", C.c_int32),
+        ("sample_cap", C.c_int32), ("chain_base", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_int64),
+        ("n_samples", C.c_double), ("sigma", C.c_double), ("sigma_lo", C.c_double), ("sigma_hi", C.c_double),
+        ("eta", C.c_double), ("target_accept", C.c_double), ("ridge", C.c_double),
+        ("free_idx", C.c_int32 * LM_MAX_FREE), ("base", C.c_double * LM_MAX_FREE),
+        ("lo", C.c_double * LM_MAX_FREE), ("hi", C.c_double * LM_MAX_FREE),
+    ]
+
+
+def mala_state_doubles(n):
+    """fp64 words of one chain's manifold-MALA state: lp, log_eps, the outside word, alpha, ld, lq_f, then u, ut, x, xt, grad [n] and
+    L [n][n]; n = the free parameters plus one if sigma is sampled."""
+    return MALA_STATE_U + 5 * n + n * n
+
+
+def mala_state_views(state, nf, sample_sigma):
+    """Named views of a state array [K, mala_state_doubles(n)] (numpy or torch), n = nf + (1 if sample_sigma else 0): lp, log_eps,
+    outside, alpha, ld, lqf [K]; u, ut, x, xt, grad [K, n]; L [K, n, n]."""
+    n = nf + (1 if sample_sigma else 0)
+    v = {"lp": state[:, MALA_STATE_LP], "log_eps": state[:, MALA_STATE_LOG_EPS], "outside": state[:, MALA_STATE_OUTSIDE],
+         "alpha": state[:, MALA_STATE_ALPHA], "ld": state[:, MALA_STATE_LD], "lqf": state[:, MALA_STATE_LQF]}
+    o = MALA_STATE_U
+    for name in ("u", "ut", "x", "xt", "grad"):
+        v[name] = state[:, o:o + n]
+        o += n
+    v["L"] = state[:, o:o + n * n].reshape(state.shape[0], n, n)
+    return v
+
+
 # Every symbol of include/ionode.h: name -> (restype, argtypes); lib() applies the table, EXPORTS is its keys.
 _D, _P, _I32, _I64, _F32 = C.POINTER(IonodeDesc), C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _SOLVE = [_D] + [_P] * 12   # ionode_dopri5: d, mlp_packed .. stats, stream -- the solve family's common prefix
@@ -255,6 +294,9 @@ PROTOTYPES = {
     # d, active, value, status, state, flag, iters, trial, samples (, stream)
     "ionode_mcmc_step": (C.c_int, [C.POINTER(IonodeMcmcDesc)] + [_P] * 9),
     "ionode_mcmc_step_host": (C.c_int, [C.POINTER(IonodeMcmcDesc)] + [_P] * 8),
+    # d, active, sse, jtr, jtj, status, state, flag, iters, trial, samples (, stream)
+    "ionode_mala_step": (C.c_int, [C.POINTER(IonodeMalaDesc)] + [_P] * 11),
+    "ionode_mala_step_host": (C.c_int, [C.POINTER(IonodeMalaDesc)] + [_P] * 10),
     "ionode_grad_reduce": (C.c_int, _REDUCE),
     "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
     "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),

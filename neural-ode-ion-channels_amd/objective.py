@@ -458,3 +458,63 @@ def population_mcmc(starts, protocols_v, data_i, t_eval, *, base_params, free=(0
     w = R * (n + 1)
     return (out[:, :w].reshape(-1, R, n + 1).contiguous(), out[:, w].contiguous(), out[:, w + 1].to(torch.int32),
             out[:, w + 2:].to(torch.int32).contiguous())
+
+
+def population_mala(starts, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds, sigma=None,
+                    sigma_bounds=None, eps0=1.0, ridge=2.0 ** -20, seed=0, max_iter=1000, thin=1, eta=0.6, target_accept=0.574,
+                    compact_every=64, prot_t0=0.0, prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
+                    obs_open_state_only=False, max_total_steps=1_000_000, max_step="auto", rtol=1e-7, atol=1e-9, group=None, device=None,
+                    solver=None, cost=None, model=capi.MODEL_HH2):
+    """Batched manifold MALA (the sampler that uses what the fit computes: the Gauss-Newton matrix J^T J / sigma^2 is the proposal's
+    metric, from iteration 0, with nothing to learn but the step size): every row of starts [K, len(free)] (or [K, len(free) + 1],
+    the last column sigma's start, when sigma is sampled) -- typically population_fit's optimum -- is the start of an independent
+    chain, all of them advanced together (mala.sample: one sensitivity.gauss_newton evaluation of K * P trajectories and one
+    ionode_mala_step launch per iteration, one read of the stop flags every compact_every iterations).
+
+    HH 2-state and 6-state only (the NN models have no tangent sweep: population_mcmc samples them).  Target, prior, bounds, sigma /
+    sigma_bounds and the returned (samples [K, R, n + 1], accept_rate [K], flag [K] int32, iterations [K, 2] int32) are
+    population_mcmc's; mcmc.rhat serves both samplers.  max_step "auto" is resolved ONCE: grad.stable_step_cap at the upper corner of
+    the box.  Sharding as population_mcmc (contiguous, or equal cost with `cost`): a chain's random numbers depend on (seed, its
+    index among all K chains, iteration, purpose, coordinate) only, so there is no communication during the run and one all-gather
+    at its end; a chain's samples do not depend on the shard it ran in.  `solver` (tests only): a stand-in with
+    sensitivity.gauss_newton's signature on CPU tensors; the step then runs as ionode_mala_step_host.
+    """
+    from . import mala
+    if model in (capi.MODEL_NNF, capi.MODEL_NND):
+        raise capi.IonodeError("population_mala: the closed-form HH 2-state and 6-state models only (the NN models have no tangent "
+                               "sweep to form the metric from); population_mcmc samples them")
+    D, npar = capi.n_state(model), capi.n_params(model)
+    free = [int(f) for f in free]
+    nf = len(free)
+    n = nf + int(sigma is None)
+    cand = np.asarray(starts, dtype=np.float64)
+    if cand.ndim != 2:
+        cand = cand.reshape(-1, nf)
+    K = cand.shape[0]
+    base = np.asarray(base_params, dtype=np.float64)
+    if base.shape != (npar,) or len(y0) != D:
+        raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
+    if bounds is None:
+        raise capi.IonodeError("population_mala: bounds = (lo, hi) are required: the box is the prior")
+    if (sigma is None) == (sigma_bounds is None):
+        raise capi.IonodeError("population_mala: exactly one of sigma (fixed noise) and sigma_bounds (sampled noise) must be given")
+    rank, world, bounds_r = distributed.population_shards(K, cost, group, "chains")
+    lo, hi = bounds_r[rank]
+    dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
+    def corner():
+        rows = base[None].copy()
+        rows[:, free] = np.asarray(bounds[1], dtype=np.float64)
+        return rows
+    max_step = _auto_max_step(max_step, model, corner, protocols_v)
+    smp, rate, flag, iters = mala.sample(model, cand[lo:hi], protocols_v, data_i, t_eval, base_params=base, free=free, log_parameters=log_parameters,
+                                         bounds=bounds, sigma=sigma, sigma_bounds=sigma_bounds, eps0=eps0, ridge=ridge, seed=seed, max_iter=max_iter,
+                                         thin=thin, eta=eta, target_accept=target_accept, compact_every=compact_every, prot_t0=prot_t0,
+                                         prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e,
+                                         obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=float(max_step),
+                                         rtol=rtol, atol=atol, device=dev, solver=solver, chain_offset=lo)
+    R = smp.shape[1]
+    out = torch.cat([smp.reshape(hi - lo, R * (n + 1)), rate[:, None], flag.double()[:, None], iters.double()], dim=1)   # [chains, R (n + 1) + 4]
+    out = distributed.all_gather_shards(out, bounds_r, rank, group)
+    w = R * (n + 1)
+    return (out[:, :w].reshape(-1, R, n + 1).contiguous(), out[:, w].contiguous(), out[:, w + 1].to(torch.int32),
+            out[:, w + 2:].to(torch.int32).contiguous())

@@ -1,6 +1,6 @@
-"""What the drivers of the three batched optimiser steps share: fit.py (Levenberg-Marquardt), cmaes.py (CMA-ES) and mcmc.py (adaptive
-Metropolis).  Each of them evaluates a trial tensor of items x rows_per_item trajectories, hands the result to its step
-(ionode_<x>_step on the current stream, ionode_<x>_step_host on CPU tensors) and, every compact_every iterations, packs the items
+"""What the drivers of the four batched optimiser and sampler steps share: fit.py (Levenberg-Marquardt), cmaes.py (CMA-ES), mcmc.py
+(adaptive Metropolis) and mala.py (manifold MALA).  Each of them evaluates a trial tensor of items x rows_per_item trajectories, hands
+the result to its step (ionode_<x>_step on the current stream, ionode_<x>_step_host on CPU tensors) and, every compact_every iterations, packs the items
 still running into the front launch slots.  The pieces of that are here; the loops stay with the drivers, which differ on purpose in
 what comes first (the solve or the step), in how often they run and in when they read the flags.
 """
@@ -13,7 +13,7 @@ from . import capi
 
 
 def fill_box(d, free, base_params, lo=None, hi=None):
-    """The box of a step descriptor (ionode_lm_desc, ionode_cmaes_desc, ionode_mcmc_desc): free_idx, lo / hi [nf] in the parameters and
+    """The box of a step descriptor (ionode_lm_desc, ionode_cmaes_desc, ionode_mcmc_desc, ionode_mala_desc): free_idx, lo / hi [nf] in the parameters and
     base.  A bound of None is no bound: with d.log_parameters a missing lower bound is the smallest normal number (the steps refuse
     non-positive bounds), else -inf."""
     nf = len(free)
