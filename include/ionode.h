@@ -439,12 +439,38 @@ int ionode_objective_backward_gc(const ionode_desc *d, int32_t objective, int32_
  * zero rows.  Reads model, state_f32, sizes, protocol grid, v_oob, ckpt, ckpt_cap, obs_*, sse_ref and the optional v_at_outputs from
  * the descriptor of the forward launch that wrote the checkpoints (ionode_dopri5 with d->ckpt set).  Refusals, all before any launch,
  * text in ionode_grad_last_error(): IONODE_ERR_ARG for a NULL descriptor, a missing required buffer (params, prot_v, t_eval,
- * n_accepted, d->ckpt), all three outputs NULL, or sums without sse_ref; IONODE_ERR_UNSUPPORTED for NN-f / NN-d (their tangent would
- * need a Jacobian-vector product through the MLP tiles) and for traj_per_image > 0.
+ * n_accepted, d->ckpt), all three outputs NULL, or sums without sse_ref; IONODE_ERR_UNSUPPORTED for NN-f / NN-d (their tangent walks
+ * the two-phase sweep's packets and needs the weights and a chunk range: ionode_tangent_sweep_nn below) and for traj_per_image > 0.
  */
 int ionode_tangent_sweep(const ionode_desc *d, const double *params, const double *prot_v, const double *prot_t,
                          const int32_t *prot_of_traj, const double *t_eval, const int32_t *n_accepted,
                          double *di_dp, double *jtr, double *jtj, void *stream);
+
+/*
+ * Forward sensitivities for NN-f / NN-d (since ABI 10, added later: new symbols only, ionode_desc and every earlier entry point
+ * unchanged).  Outputs, rule of differentiation and dtypes as ionode_tangent_sweep (NPAR = 8; NN-f: the columns p1..p4 are exactly
+ * zero).  The state the net sees is one scalar, a, and ionode_dopri5_backward_recompute already computes d net / d a of every
+ * (trajectory, accepted step, stage) into its packets; so per chunk [it_begin, it_end) of the two-phase sweep's iterations this entry
+ * point launches two kernels on `stream`: that recompute kernel without grad_y and without records (the packets' stage fields alone),
+ * and the tangent walk over the packets (csrc/ionode_tangent_nn.hpp), forward in time.  Iteration numbering is the backward sweep's
+ * (trajectory b runs its step s at it = n_accepted[b] - 1 - s, n_iter = max n_accepted + 1), so forward in time is DESCENDING: call
+ * the chunks from [n_iter - c, n_iter) down to [0, c).  The same bits for any chunking and any batch around a trajectory.
+ *   grad_image  ionode_grad_pack's image of the one weight set
+ *   packets     [ceil(B/16)][it_end - it_begin][ionode_grad_packet_doubles()] fp64 scratch of the chunk
+ *   state       [B][ionode_tangent_nn_state_doubles()] fp64: S, Kd_7 and the running sums between the launches; the launch with
+ *               it_end == n_iter does not read it
+ *   di_dp       rows are written as their steps are walked (row 0 and failed trajectories' rows by the launch with it_end == n_iter)
+ *   jtr, jtj    written by the launch with it_begin == 0
+ * Refusals, all before any launch, text in ionode_grad_last_error(): IONODE_ERR_ARG for a NULL descriptor, a missing required buffer
+ * (grad_image, params, prot_v, t_eval, n_accepted, packets, state, d->ckpt), all three outputs NULL, sums without sse_ref (the trace
+ * alone needs none), a bad iteration range or more than 65535 x 4 iterations; IONODE_ERR_UNSUPPORTED for the closed-form models
+ * (ionode_tangent_sweep serves those), for traj_per_image > 0 and for a width or depth outside the backward sweep's compiled variants.
+ */
+size_t ionode_tangent_nn_state_doubles(void);
+int ionode_tangent_sweep_nn(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
+                            const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
+                            const double *t_eval, const int32_t *n_accepted, double *packets, double *state,
+                            double *di_dp, double *jtr, double *jtj, void *stream);
 
 /* floats of one slab's partial gradient: [NP][4]{db0, dW0[.][0], dW0[.][1], 0} | L x (dW_l [NP][NP] + db_l [NP]) | dwl [NP] +
  * {dbl, 0, 0, 0}, NP = 16 * ceil(N / 16), rows/columns >= N are padding */

@@ -53,6 +53,10 @@ OBJECTIVE_BUFFERS = {
     "ionode_objective_backward_gc": SWEEP_BUFFERS["ionode_dopri5_backward_sse_gc"],
 }
 
+# the NN models' tangent sweep (ionode_tangent_sweep_nn): its buffers in ABI order -- between (d, it_begin, it_end, n_iter) and stream
+TANGENT_NN_BUFFERS = ("grad_image", "params", "prot_v", "prot_t", "prot_of_traj", "t_eval", "n_accepted", "packets", "state",
+                      "di_dp", "jtr", "jtj")
+
 
 def n_state(model):
     return 6 if model == MODEL_MARKOV6 else 2
@@ -283,8 +287,10 @@ PROTOTYPES = {
     **{name: (C.c_int, [_D] + [_I32] * 3 + [_P] * (len(buffers) + 1)) for name, buffers in SWEEP_BUFFERS.items()},
     **{name: (C.c_int, [_D] + [_I32] * 4 + [_P] * (len(buffers) + 1)) for name, buffers in OBJECTIVE_BUFFERS.items()},
     "ionode_tangent_sweep": (C.c_int, [_D] + [_P] * 10),   # params, prot_v, prot_t, prot_of_traj, t_eval, n_accepted, di_dp, jtr, jtj, stream
+    "ionode_tangent_nn_state_doubles": (C.c_size_t, []),
+    "ionode_tangent_sweep_nn": (C.c_int, [_D] + [_I32] * 3 + [_P] * (len(TANGENT_NN_BUFFERS) + 1)),
     # d, active, sse, jtr, jtj, status, state, flag, iters, trial (, stream)
-    "ionode_lm_step": (C.c_int, [C.POINTER(IonodeLmDesc)] + [_P] * 10),
+    "ionode_lm_step":(C.c_int, [C.POINTER(IonodeLmDesc)] + [_P] * 10),
     "ionode_lm_step_host": (C.c_int, [C.POINTER(IonodeLmDesc)] + [_P] * 9),
     # d, active, value, status, state, flag, iters, trial (, stream)
     "ionode_cmaes_step": (C.c_int, [C.POINTER(IonodeCmaesDesc)] + [_P] * 8),

@@ -9,6 +9,7 @@
 #include "ionode_grad_gen_plan.hpp"
 #include "ionode_host.hpp"
 #include "ionode_tangent.hpp"
+#include "ionode_tangent_nn.hpp"
 
 #include "ionode_step_capi.hpp"
 
@@ -485,6 +486,60 @@ int ionode_tangent_sweep(const ionode_desc *d, const double *params, const doubl
   t.di_dp = di_dp; t.jtr = jtr; t.jtj = jtj;
   ionode::launch_tangent(d->model, d->state_f32 ? 1 : 0, t, reinterpret_cast<hipStream_t>(stream));
   const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return refuse(IONODE_ERR_LAUNCH, "%s", hipGetErrorString(err));
+  return IONODE_OK;
+}
+
+// ---- tangent sweep of NN-f / NN-d (ionode_tangent_nn.hpp): per chunk the recompute kernel without grad_y and without records -- the
+// packets' stage fields alone -- then the tangent walk over them, both on `stream`.  The recompute launcher is reached here and not
+// through ionode_dopri5_backward_recompute_sse, which requires d->sse_ref: the trace needs none.  Every refusal is decided before the
+// first launch.
+size_t ionode_tangent_nn_state_doubles(void) { return (size_t)ionode::TANGENT_NN_STATE; }
+
+int ionode_tangent_sweep_nn(const ionode_desc *d, int32_t it_begin, int32_t it_end, int32_t n_iter, const float *grad_image,
+                            const double *params, const double *prot_v, const double *prot_t, const int32_t *prot_of_traj,
+                            const double *t_eval, const int32_t *n_accepted, double *packets, double *state,
+                            double *di_dp, double *jtr, double *jtj, void *stream) {
+  constexpr const char *WHO = "ionode_tangent_sweep_nn";
+  if (!d) return refuse(IONODE_ERR_ARG, "null descriptor");
+  if (d->model == IONODE_MODEL_HH2 || is_m6(d)) return refuse(IONODE_ERR_UNSUPPORTED, "%s: NN-f / NN-d only (closed-form models: ionode_tangent_sweep)", WHO);
+  if (!is_nn(d)) return refuse(IONODE_ERR_UNSUPPORTED, "%s: unknown model", WHO);
+  if (d->traj_per_image > 0) return refuse(IONODE_ERR_UNSUPPORTED, "%s: traj_per_image must be 0", WHO);
+  if (!desc_consistent(d)) return refuse(IONODE_ERR_ARG, "inconsistent descriptor");
+  if (!grad_image || !params || !prot_v || !t_eval || !n_accepted || !packets || !state || !d->ckpt || d->ckpt_cap < 1)
+    return refuse(IONODE_ERR_ARG, "%s: required buffer is NULL (ckpt / ckpt_cap come from the descriptor)", WHO);
+  if (!di_dp && !jtr && !jtj) return refuse(IONODE_ERR_ARG, "%s: nothing to compute (di_dp, jtr and jtj are all NULL)", WHO);
+  if ((jtr || jtj) && !d->sse_ref) return refuse(IONODE_ERR_ARG, "%s: jtr / jtj need the reference currents (sse_ref comes from the descriptor)", WHO);
+  if (it_begin < 0 || it_end <= it_begin || it_end > n_iter) return refuse(IONODE_ERR_ARG, "bad iteration range");
+  if ((int64_t)it_end - it_begin > (int64_t)65535 * 4)
+    return refuse(IONODE_ERR_ARG, "%s: at most 65535 x 4 iterations per launch (HIP's grid.y limit): split the range", WHO);
+  if (d->mlp_layers < 1 || d->mlp_width < 1) return refuse(IONODE_ERR_ARG, "bad MLP shape");
+  const int NP = np_of(d->mlp_width), NT = NP / 16, L = d->mlp_layers;
+  const SweepFn recompute = find_sweep(Sweep::Recompute, d, NT);
+  const size_t net_lds = ionode::grad_lds_bytes(L, NT);
+  if (!recompute || L > 15 || net_lds + 16 + ionode::grad_walk_lds_bytes() > 160 * 1024)   // (the two-phase backward sweep's own rule)
+    return refuse(IONODE_ERR_UNSUPPORTED, "%s: (L, N) outside the backward sweep's compiled variants (N pads to 16, 112, 208 or 512; at most 15 hidden layers)", WHO);
+
+  ionode::TArgs t;
+  memset(&t, 0, sizeof t);
+  GArgs &a = t.g;
+  a.k.params = params; a.k.prot_v = prot_v; a.k.prot_t = prot_t; a.k.prot_of_traj = prot_of_traj; a.k.t_eval = t_eval;
+  a.k.B = d->n_traj; a.k.Nt = d->n_out; a.k.P = d->n_prot; a.k.Np = d->prot_n; a.k.n_params = d->n_params;
+  a.k.L = L; a.k.N = d->mlp_width; a.k.NP = NP; a.k.NT = NT;
+  a.k.prot_t0 = d->prot_t0; a.k.prot_dt = d->prot_dt; a.k.prot_rdt = 1.0 / d->prot_dt; a.k.v_oob = d->v_oob;
+  a.img = grad_image; a.ckpt = d->ckpt; a.ckpt_cap = d->ckpt_cap; a.nacc = n_accepted;
+  a.record_floats = ionode::grad_record_floats(L, NT); a.packets = packets;   // (grad_y, records: NULL -- the packets' stage fields alone)
+  a.it_begin = it_begin; a.it_end = it_end; a.n_iter = n_iter;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  recompute(a, (unsigned)((a.k.B + 15) / 16), net_lds, s);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return refuse(IONODE_ERR_LAUNCH, "%s", hipGetErrorString(err));
+  // what the walk reads beside the packets: the carried state, the observation model and (for the sums) the reference currents
+  a.state = state; a.sse_ref = d->sse_ref; a.v_tab = d->v_at_outputs;
+  a.obs_g = d->obs_g; a.obs_e = d->obs_e; a.obs_open = d->obs_open_state_only ? 1 : 0;
+  t.di_dp = di_dp; t.jtr = jtr; t.jtj = jtj;
+  ionode::launch_tangent_nn(d->model, d->state_f32 ? 1 : 0, t, s);
+  err = hipGetLastError();
   if (err != hipSuccess) return refuse(IONODE_ERR_LAUNCH, "%s", hipGetErrorString(err));
   return IONODE_OK;
 }

@@ -1,4 +1,4 @@
-"""Multi-start Levenberg-Marquardt for a whole population of candidates (closed-form HH 2-state and 6-state models).
+"""Multi-start Levenberg-Marquardt for a whole population of candidates (closed-form HH 2-state and 6-state models; NN-f / NN-d with weights).
 
 Reference: the candidate-model fits (train-d0.py:508-540: a PINTS optimiser on SumOfSquaresError under a LogTransformation, one
 candidate at a time over a process pool).  Here every candidate of a population is a start of a damped Gauss-Newton iteration,
@@ -16,7 +16,8 @@ and the candidates still running are packed into the front launch slots (the ste
 solve after at most `compact_every` further iterations.  A candidate's iterates do not depend on the others: compaction, the batch
 around it and the sharding of objective.population_fit leave its bits alone.
 
-Out of scope: the NN models (their tangent sweep is refused) and CMA-ES -- both are cmaes.py, the derivative-free sibling --,
+NN models: NN-f and NN-d are fitted too when their weights are given (one shared weight set; sensitivity.py's NN route); without
+weights they are refused as before.  Out of scope: CMA-ES -- cmaes.py, the derivative-free sibling --, a weight set per candidate,
 sensitivities with respect to y0.  A noise model (the fit minimises the plain sum of squares) and the posterior around a fit
 are mcmc.py: adaptive Metropolis, objective.population_mcmc.
 """
@@ -70,7 +71,8 @@ def lm_step(desc, active, sse, jtr, jtj, status, state, flag, iters, trial):
 def levenberg_marquardt(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds=None,
                         prot_t0=0.0, prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
                         obs_open_state_only=False, max_total_steps=1_000_000, max_step=0.0, rtol=1e-7, atol=1e-9, device=None, solver=None,
-                        max_iter=50, gtol=1e-8, xtol=1e-8, ftol=1e-8, lam_init=1e-3, compact_every=4, callback=None):
+                        max_iter=50, gtol=1e-8, xtol=1e-8, ftol=1e-8, lam_init=1e-3, compact_every=4, callback=None, weights=None,
+                        mlp_layers=0, mlp_width=0, weights_key=None):
     """Fit one batch of candidates on one device: x0 [n, nf] starting values of the free rate parameters, one fit each.
 
     protocols_v [P, Np], data_i [P, Nt], t_eval [Nt] (uniform: sensitivity.gauss_newton's rule), base_params [8 | 12]; bounds =
@@ -83,12 +85,18 @@ def levenberg_marquardt(model, x0, protocols_v, data_i, t_eval, *, base_params, 
     on the device: the best accepted point of every start; sse = inf and flag LM_NONFINITE where the start itself could not be
     evaluated.  `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature on CPU tensors; the step is then
     ionode_lm_step_host and nothing needs a GPU.  The product default has no CPU path.
-    Out of scope: NN models and CMA-ES (both: cmaes.minimise), y0 sensitivities (module docstring); a noise model is mcmc.sample."""
+    NN models (NN-f, NN-d): with weights [n] (one flat state dict shared by every candidate), mlp_layers, mlp_width and weights_key
+    (sensitivity.gauss_newton's) they are fitted like the others, `free` indexing their 8 rate parameters (NN-f: 4..7 only); without
+    weights they are refused, and so is a weight set per candidate [C, n].
+    Out of scope: CMA-ES and NN models without weights (cmaes.minimise), y0 sensitivities (module docstring); a noise model is mcmc.sample."""
     from . import batched, sensitivity
-    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
-        raise capi.IonodeError("fit.levenberg_marquardt: HH 2-state and 6-state models only (the NN models' tangent sweep is refused)")
-    D, npar = capi.n_state(model), capi.n_params(model)
+    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6, capi.MODEL_NNF, capi.MODEL_NND):
+        raise capi.IonodeError("fit.levenberg_marquardt: unknown model (HH 2-state and 6-state models, NN-f and NN-d with weights)")
     free = [int(f) for f in free]
+    mlp = sensitivity.nn_route("fit.levenberg_marquardt", model, weights, mlp_layers, mlp_width, free)
+    if mlp:
+        mlp["weights_key"] = weights_key
+    D, npar = capi.n_state(model), capi.n_params(model)
     nf = len(free)
     x0 = np.asarray(x0, dtype=np.float64).reshape(-1, nf) if nf else np.zeros((0, 0))
     base = np.asarray(base_params, dtype=np.float64)
@@ -112,7 +120,7 @@ def levenberg_marquardt(model, x0, protocols_v, data_i, t_eval, *, base_params, 
         rows = n_act * P
         sse, jtr, jtj, status = solve(model, trial, pv, y0t[:rows], te, ref, prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=pot[:rows],
                                       obs_g=obs_g, obs_e=obs_e, obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps,
-                                      max_step=max_step, rtol=rtol, atol=atol)
+                                      max_step=max_step, rtol=rtol, atol=atol, **mlp)
         lm_step(desc, active, sse.contiguous(), jtr.contiguous(), jtj.contiguous(), status.to(torch.int32).contiguous(), state, flag, iters,
                 trial)
         if callback is not None:

@@ -1,6 +1,6 @@
 """Batched manifold MALA: many independent chains sampling the posterior of the free rate parameters (and, optionally, of the noise
 level) under a Gaussian noise model, advanced together, with the Gauss-Newton matrix the library already sums as the proposal's
-metric (HH 2-state and 6-state: the models with a tangent sweep).
+metric (HH 2-state and 6-state, and NN-f / NN-d with their weights: the models with a tangent sweep).
 
 mcmc.py's adaptive Metropolis learns the shape of the posterior from its own history.  Under the Gaussian noise model J^T J / sigma^2
 is the expected Fisher information -- the local metric of the posterior, at every point, from iteration 0 -- and
@@ -22,8 +22,8 @@ flags are read once and the chains still going are packed into the front launch 
 (seed, chain, iteration, purpose, coordinate pair): compaction, the batch around a chain and the sharding of
 objective.population_mala leave its bits alone, and the host mirror (ionode_mala_step_host) equals the kernel bit for bit.
 
-Out of scope: HMC / NUTS, the full manifold MALA with the metric's derivatives, tempering, the NN models (no tangent sweep:
-objective.population_mcmc samples them), priors other than the box, per-protocol noise, bit-compatibility with PINTS.
+Out of scope: HMC / NUTS, the full manifold MALA with the metric's derivatives, tempering, NN models without weights or with a weight
+set per chain (sensitivity.py's NN route takes one weight set), priors other than the box, per-protocol noise, bit-compatibility with PINTS.
 """
 import numpy as np
 import torch
@@ -108,11 +108,14 @@ def mala_step(desc, active, sse, jtr, jtj, status, state, flag, iters, trial, sa
 def sample(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds, sigma=None,
            sigma_bounds=None, eps0=1.0, ridge=2.0 ** -20, seed=0, max_iter=1000, thin=1, eta=0.6, target_accept=0.574, compact_every=64,
            prot_t0=0.0, prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False,
-           max_total_steps=1_000_000, max_step=0.0, rtol=1e-7, atol=1e-9, device=None, solver=None, callback=None, chain_offset=0):
+           max_total_steps=1_000_000, max_step=0.0, rtol=1e-7, atol=1e-9, device=None, solver=None, callback=None, chain_offset=0,
+           weights=None, mlp_layers=0, mlp_width=0, weights_key=None):
     """Sample the posterior of the free rate parameters given data_i with K independent manifold-MALA chains on one device: x0 [K, nf]
     (or [K, nf + 1] with sigma's start as the last column when sigma is sampled), one chain per row -- typically fit.py's optimum.
 
-    model: HH 2-state or 6-state (the NN models have no tangent sweep: objective.population_mcmc samples them).  protocols_v [P, Np],
+    model: HH 2-state or 6-state, or -- with weights [n] (one flat state dict shared by every chain), mlp_layers, mlp_width and
+    weights_key (sensitivity.gauss_newton's) -- NN-f or NN-d, `free` indexing their 8 rate parameters (NN-f: 4..7 only); an NN model
+    without weights is refused (objective.population_mcmc needs them as well), and so is a weight set per chain.  protocols_v [P, Np],
     data_i [P, Nt], t_eval [Nt] (uniform: sensitivity.gauss_newton's rule), base_params [8 | 12].  bounds = (lo [nf], hi [nf]) in the
     parameters, finite: the box is the prior -- uniform in the search space, so LOG-UNIFORM in the parameters with log_parameters.
     Exactly one of sigma (the fixed noise level of the Gaussian likelihood) and sigma_bounds = (lo, hi) (sigma is sampled as log
@@ -128,13 +131,13 @@ def sample(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2
     `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature on CPU tensors; the step is then
     ionode_mala_step_host and nothing needs a GPU.  The product default has no CPU path."""
     from . import batched, sensitivity
-    if model in (capi.MODEL_NNF, capi.MODEL_NND):
-        raise capi.IonodeError("mala.sample: the closed-form HH 2-state and 6-state models only (the NN models have no tangent sweep "
-                               "to form the metric from); objective.population_mcmc samples them")
-    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
+    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6, capi.MODEL_NNF, capi.MODEL_NND):
         raise capi.IonodeError(f"mala.sample: unknown model {model}")
-    D, npar = capi.n_state(model), capi.n_params(model)
     free = [int(f) for f in free]
+    mlp = sensitivity.nn_route("mala.sample", model, weights, mlp_layers, mlp_width, free)
+    if mlp:
+        mlp["weights_key"] = weights_key
+    D, npar = capi.n_state(model), capi.n_params(model)
     nf = len(free)
     if not 1 <= nf <= capi.LM_MAX_FREE:
         raise capi.IonodeError(f"mala.sample: 1 .. {capi.LM_MAX_FREE} free parameters, got {nf}")
@@ -169,7 +172,7 @@ def sample(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2
         rows = n_act * P
         sse, jtr, jtj, status = solve(model, trial, pv, y0t[:rows], te, ref, prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=pot[:rows],
                                       obs_g=obs_g, obs_e=obs_e, obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps,
-                                      max_step=max_step, rtol=rtol, atol=atol)
+                                      max_step=max_step, rtol=rtol, atol=atol, **mlp)
         mala_step(desc, active, sse.contiguous(), jtr.contiguous(), jtj.contiguous(), status.to(torch.int32).contiguous(), state, flag, iters,
                   trial, samples)
         if callback is not None:

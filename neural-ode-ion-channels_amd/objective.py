@@ -239,7 +239,7 @@ def _population_error_s1(kind, candidates, protocols_v, data_i, t_eval, *, base_
 def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=False, prot_t0=0.0,
                             prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False,
                             max_total_steps=1_000_000, max_step="auto", group=None, device=None, solver=None, cost=None,
-                            model=capi.MODEL_HH2):
+                            model=capi.MODEL_HH2, weights=None, mlp_layers=0, mlp_width=0, weights_key=None):
     """Sum-of-squares error of every candidate with its gradient AND its Gauss-Newton Hessian in the free parameters: what a
     Gauss-Newton / Levenberg-Marquardt step or a Fisher-information estimate needs, from forward sensitivities
     (sensitivity.gauss_newton: PINTS ForwardModelS1.simulateS1 contracted in the kernel, no trace of size [C * P, Nt] is written).
@@ -251,15 +251,21 @@ def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_par
     train-d0.py:511), g_j p_j and H_jl p_j p_l.  A candidate any of whose solves failed gets sse = inf and ZERO g and H.
     `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature, so the sharding / all-gather logic can run without a
     GPU.  The optimiser built on these sums is population_fit (fit.py: Levenberg-Marquardt with the reduction, the damping, the
-    step and its acceptance in one kernel); no y0 sensitivities, no NN models, no absolute-error variant (sensitivity's module
-    docstring).
+    step and its acceptance in one kernel); no y0 sensitivities, no absolute-error variant (sensitivity's module docstring).
+    NN models (NN-f, NN-d): with weights [n] -- ONE flat state dict shared by the population --, mlp_layers, mlp_width and weights_key
+    they are served through sensitivity.py's NN route, `free` indexing their 8 rate parameters (NN-f: 4..7 only: it has no p1..p4);
+    max_step "auto" resolves as everywhere in this module for them: no cap.  Without weights they are refused, and so is a weight set
+    per candidate, weights [C, n]: the tangent sweep differentiates one weight set.
     """
     who = "population_gauss_newton"
     from . import sensitivity
-    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
-        raise capi.IonodeError(f"{who}: HH 2-state and 6-state models only")
-    D, npar = (6, 12) if model == capi.MODEL_MARKOV6 else (2, 8)
+    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6, capi.MODEL_NNF, capi.MODEL_NND):
+        raise capi.IonodeError(f"{who}: unknown model (HH 2-state and 6-state models, NN-f and NN-d with weights)")
     free = [int(f) for f in free]
+    mlp = sensitivity.nn_route(who, model, weights, mlp_layers, mlp_width, free)
+    if mlp:
+        mlp["weights_key"] = weights_key
+    D, npar = capi.n_state(model), capi.n_params(model)
     cand = np.asarray(candidates, dtype=np.float64).reshape(-1, len(free))
     C, P = cand.shape[0], np.asarray(protocols_v).shape[0]
     base = np.asarray(base_params, dtype=np.float64)
@@ -283,7 +289,7 @@ def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_par
                                       torch.as_tensor(np.asarray(t_eval), dtype=torch.float64, device=dev).contiguous(),
                                       torch.as_tensor(np.asarray(data_i), dtype=torch.float64, device=dev).contiguous(),
                                       prot_t0=prot_t0, prot_dt=prot_dt, prot_of_traj=pot, obs_g=obs_g, obs_e=obs_e,
-                                      obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=max_step)
+                                      obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=max_step, **mlp)
         ok = (status.reshape(n, P) == 0).all(dim=1)
         err = sse.reshape(n, P).sum(dim=1)
         g = 2.0 * jtr.reshape(n, P, npar).sum(dim=1)[:, free]
@@ -301,7 +307,8 @@ def population_gauss_newton(candidates, protocols_v, data_i, t_eval, *, base_par
 def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds=None, prot_t0=0.0,
                    prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False,
                    max_total_steps=1_000_000, max_step="auto", rtol=1e-7, atol=1e-9, group=None, device=None, solver=None, cost=None,
-                   model=capi.MODEL_HH2, max_iter=50, gtol=1e-8, xtol=1e-8, ftol=1e-8, lam_init=1e-3, compact_every=4):
+                   model=capi.MODEL_HH2, max_iter=50, gtol=1e-8, xtol=1e-8, ftol=1e-8, lam_init=1e-3, compact_every=4, weights=None,
+                   mlp_layers=0, mlp_width=0, weights_key=None):
     """Multi-start Levenberg-Marquardt: every candidate is the start of a fit of the free parameters to data_i, all of them iterated
     together (fit.levenberg_marquardt: one sensitivity.gauss_newton evaluation and one ionode_lm_step launch per iteration, one read
     of the stop flags every compact_every iterations).
@@ -319,15 +326,20 @@ def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free
     others, so there is no communication during the fit and one all-gather of [C, len(free) + 4] at its end.  A candidate's result
     does not depend on the shard it ran in.  `solver` (tests only): a stand-in with sensitivity.gauss_newton's signature on CPU
     tensors -- the step then runs as ionode_lm_step_host and the loop, the compaction and the all-gather need no GPU.
-    Out of scope: the NN models (their tangent sweep is refused) and CMA-ES -- both are population_cmaes / cmaes.py --, sensitivities with
-    respect to y0.  A noise model and the posterior around a fit are population_mcmc / mcmc.py.
+    NN models (NN-f, NN-d -- the hybrid model's HH rates around a trained net are what train-d0.py fits): with weights [n] (ONE flat
+    state dict shared by every start), mlp_layers, mlp_width and weights_key as population_gauss_newton; `free` indexes their 8 rate
+    parameters (NN-f: 4..7 only); max_step "auto" is no cap for them, as in population_cmaes.  Without weights they are refused, and so
+    is a weight set per candidate [C, n].
+    Out of scope: CMA-ES (population_cmaes / cmaes.py, which also takes a population of nets), sensitivities with
+    respect to y0.  A noise model and the posterior around a fit are population_mcmc / mcmc.py and population_mala / mala.py.
     """
     who = "population_fit"
-    from . import fit
-    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6):
-        raise capi.IonodeError(f"{who}: HH 2-state and 6-state models only")
-    D, npar = (6, 12) if model == capi.MODEL_MARKOV6 else (2, 8)
+    from . import fit, sensitivity
+    if model not in (capi.MODEL_HH2, capi.MODEL_MARKOV6, capi.MODEL_NNF, capi.MODEL_NND):
+        raise capi.IonodeError(f"{who}: unknown model (HH 2-state and 6-state models, NN-f and NN-d with weights)")
     free = [int(f) for f in free]
+    sensitivity.nn_route(who, model, weights, mlp_layers, mlp_width, free)
+    D, npar = capi.n_state(model), capi.n_params(model)
     nf = len(free)
     cand = np.asarray(candidates, dtype=np.float64).reshape(-1, nf)
     C = cand.shape[0]
@@ -343,7 +355,8 @@ def population_fit(candidates, protocols_v, data_i, t_eval, *, base_params, free
                                                   state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e, obs_open_state_only=obs_open_state_only,
                                                   max_total_steps=max_total_steps, max_step=float(max_step), rtol=rtol, atol=atol, device=dev,
                                                   solver=solver, max_iter=max_iter, gtol=gtol, xtol=xtol, ftol=ftol, lam_init=lam_init,
-                                                  compact_every=compact_every)
+                                                  compact_every=compact_every, weights=weights, mlp_layers=mlp_layers, mlp_width=mlp_width,
+                                                  weights_key=weights_key)
     out = torch.cat([x, sse[:, None], flag.double()[:, None], iters.double()], dim=1)   # [n, nf + 4]
     out = distributed.all_gather_shards(out, bounds_r, rank, group)
     return out[:, :nf].contiguous(), out[:, nf].contiguous(), out[:, nf + 1].to(torch.int32), out[:, nf + 2:].to(torch.int32).contiguous()
@@ -464,14 +477,17 @@ def population_mala(starts, protocols_v, data_i, t_eval, *, base_params, free=(0
                     sigma_bounds=None, eps0=1.0, ridge=2.0 ** -20, seed=0, max_iter=1000, thin=1, eta=0.6, target_accept=0.574,
                     compact_every=64, prot_t0=0.0, prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
                     obs_open_state_only=False, max_total_steps=1_000_000, max_step="auto", rtol=1e-7, atol=1e-9, group=None, device=None,
-                    solver=None, cost=None, model=capi.MODEL_HH2):
+                    solver=None, cost=None, model=capi.MODEL_HH2, weights=None, mlp_layers=0, mlp_width=0, weights_key=None):
     """Batched manifold MALA (the sampler that uses what the fit computes: the Gauss-Newton matrix J^T J / sigma^2 is the proposal's
     metric, from iteration 0, with nothing to learn but the step size): every row of starts [K, len(free)] (or [K, len(free) + 1],
     the last column sigma's start, when sigma is sampled) -- typically population_fit's optimum -- is the start of an independent
     chain, all of them advanced together (mala.sample: one sensitivity.gauss_newton evaluation of K * P trajectories and one
     ionode_mala_step launch per iteration, one read of the stop flags every compact_every iterations).
 
-    HH 2-state and 6-state only (the NN models have no tangent sweep: population_mcmc samples them).  Target, prior, bounds, sigma /
+    HH 2-state and 6-state, and -- with weights [n] (ONE flat state dict shared by every chain), mlp_layers, mlp_width, weights_key as
+    population_gauss_newton -- NN-f and NN-d (`free` indexes their 8 rate parameters, NN-f: 4..7 only; "auto" is no cap for them).
+    An NN model without weights is refused (population_mcmc needs them as well), and so is a weight set per chain [K, n].
+    Target, prior, bounds, sigma /
     sigma_bounds and the returned (samples [K, R, n + 1], accept_rate [K], flag [K] int32, iterations [K, 2] int32) are
     population_mcmc's; mcmc.rhat serves both samplers.  max_step "auto" is resolved ONCE: grad.stable_step_cap at the upper corner of
     the box.  Sharding as population_mcmc (contiguous, or equal cost with `cost`): a chain's random numbers depend on (seed, its
@@ -479,12 +495,10 @@ def population_mala(starts, protocols_v, data_i, t_eval, *, base_params, free=(0
     at its end; a chain's samples do not depend on the shard it ran in.  `solver` (tests only): a stand-in with
     sensitivity.gauss_newton's signature on CPU tensors; the step then runs as ionode_mala_step_host.
     """
-    from . import mala
-    if model in (capi.MODEL_NNF, capi.MODEL_NND):
-        raise capi.IonodeError("population_mala: the closed-form HH 2-state and 6-state models only (the NN models have no tangent "
-                               "sweep to form the metric from); population_mcmc samples them")
-    D, npar = capi.n_state(model), capi.n_params(model)
+    from . import mala, sensitivity
     free = [int(f) for f in free]
+    sensitivity.nn_route("population_mala", model, weights, mlp_layers, mlp_width, free)
+    D, npar = capi.n_state(model), capi.n_params(model)
     nf = len(free)
     n = nf + int(sigma is None)
     cand = np.asarray(starts, dtype=np.float64)
@@ -511,7 +525,8 @@ def population_mala(starts, protocols_v, data_i, t_eval, *, base_params, free=(0
                                          thin=thin, eta=eta, target_accept=target_accept, compact_every=compact_every, prot_t0=prot_t0,
                                          prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e,
                                          obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=float(max_step),
-                                         rtol=rtol, atol=atol, device=dev, solver=solver, chain_offset=lo)
+                                         rtol=rtol, atol=atol, device=dev, solver=solver, chain_offset=lo, weights=weights, mlp_layers=mlp_layers,
+                                         mlp_width=mlp_width, weights_key=weights_key)
     R = smp.shape[1]
     out = torch.cat([smp.reshape(hi - lo, R * (n + 1)), rate[:, None], flag.double()[:, None], iters.double()], dim=1)   # [chains, R (n + 1) + 4]
     out = distributed.all_gather_shards(out, bounds_r, rank, group)
