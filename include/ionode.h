@@ -933,6 +933,60 @@ int ionode_mala_step(const ionode_mala_desc *d, const int32_t *active, const dou
 int ionode_mala_step_host(const ionode_mala_desc *d, const int32_t *active, const double *sse, const double *jtr, const double *jtj,
                           const int32_t *status, double *state, int32_t *flag, int32_t *iters, double *trial, double *samples);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Multi-exponential fits of a(t) segments: the objective a CMA-ES run minimises, and the fitted curve with its derivatives
+ * (new symbols, ABI stays 10).
+ * The reference's real-data route turns a measured current into a(t), da/dt and d2a/dt2 with one tri- or bi-exponential fit
+ * per constant-voltage segment (train-r1.py:427-451: tri_exp / bi_exp and their derivatives; :487-494: f = sqrt(mean((model -
+ * a)^2)) minimised per segment) and hands its hardest segments, the -90 mV steps, to PINTS' CMA-ES (train-r1.py:553-555, :641;
+ * train-r2.py:595, :671).  Here K runs -- every segment of a protocol, each restarted a few times -- advance together: a
+ * generation of all runs is ionode_multi_exp_objective on the trial tensor, then ionode_cmaes_step (above, n_prot = 1, n_params
+ * = n_free = 5 or 7, log_parameters = 0) on its value / status, on one stream with no host synchronisation between them.
+ *
+ * The model.  n_params = 7 (tri-exponential, NT = 3) or 5 (bi-exponential, NT = 2); x = (A_1, b_1, ..., A_NT, b_NT, c) and
+ *   m(t) = ((A_1 e_1 + A_2 e_2) + A_3 e_3) + c,  e_j = exp((-b_j) t),
+ * summed from the first term with the offset added last (train-r1.py:427-451's order); exp is the library's deterministic
+ * exponential (the step units' operation sequence: the only fma of these units is inside it).
+ *
+ * ionode_multi_exp_objective.  The indexing is ionode_cmaes_step's with P = 1: launch slot s holds run active[s] (active ==
+ * NULL: run s), candidate k of the slot is row s lambda + k of trial [n_active lambda][n_params], value and status are indexed by
+ * row.  Run r fits segment seg_of_run[r] (int32 [n_run]); several runs may share a segment: those are the restarts.  Segment g
+ * owns the samples seg_off[g] .. seg_off[g + 1] - 1 (int64 [segments + 1]) of t_rel and a (fp64): t_rel is the time measured
+ * from the segment's first fitted sample, a the activation estimate.  With n = the segment's samples
+ *   value[row] = sqrt(sum_k (m(t_k) - a_k)^2 / n)   (the reference's f),  status[row] = 0;
+ * an empty segment (n = 0, or a negative segment index) gives value = +inf, status = 1.  Non-finite parameters or an
+ * exponential that overflows simply propagate (+inf or NaN in value, status 0): ionode_cmaes_step ranks a NaN as +inf.  A slot
+ * whose active[] entry names no run is not touched.  The caller guarantees seg_of_run[r] < segments.
+ * Execution model: one 256-lane workgroup per row.  Lane l sums the squared residuals of the samples k = l, l + 256, l + 512,
+ * ... in ascending order.  The 256 partial sums are combined in ONE WRITTEN ORDER: inside each of the four wavefronts an
+ * xor-butterfly, v_l <- v_l + v_(l xor s) for the strides s = 32, 16, 8, 4, 2, 1 in that order (both partners of an exchange
+ * form the same sum, so after the last stride every lane of wavefront i holds w_i); then (w_0 + w_1) + (w_2 + w_3) through LDS,
+ * the division by n and the square root.  No atomics, no scratch.
+ *
+ * ionode_multi_exp_eval.  x [n_seg][n_params] fp64, one fitted parameter vector per segment; segment g's full grid -- which
+ * includes the samples the capacitance mask removed from the fit -- is full_off[g] .. full_off[g + 1] - 1 (int64 [n_seg + 1])
+ * of t_full (fp64, measured from the segment's first FITTED sample).  For every sample the fitted curve and its first and
+ * second time derivative (train-r1.py:430-438, :444-451) are written to a_fit / dadt / d2adt2: the term of order q is
+ * ((-b_j)^q A_j) e_j with the coefficient formed first, (-b)^2 written b b; each sum starts from its first term; the offset is
+ * added for q = 0 only.  One lane per sample: 32 workgroups of 256 lanes stride over a segment's grid.
+ *
+ * The _host entry points run the same functions on host pointers with no HIP call, lane after lane in the written order;
+ * their results equal the kernels' bit for bit.
+ * Refusals, all before anything is touched, text in the gradient path's error string: IONODE_ERR_ARG for a NULL buffer
+ * (active may be NULL), n_params not 5 or 7, lambda outside 2 .. IONODE_CMAES_MAX_LAMBDA, n_run / n_active < 1 or n_active >
+ * n_run, n_active lambda beyond 2^31 - 1 rows, n_seg < 1.
+ * ------------------------------------------------------------------------------------------------------------------- */
+int ionode_multi_exp_objective(int32_t n_run, int32_t n_active, int32_t lambda, int32_t n_params, const int32_t *active,
+                               const int32_t *seg_of_run, const int64_t *seg_off, const double *t_rel, const double *a, const double *trial,
+                               double *value, int32_t *status, void *stream);
+int ionode_multi_exp_objective_host(int32_t n_run, int32_t n_active, int32_t lambda, int32_t n_params, const int32_t *active,
+                                    const int32_t *seg_of_run, const int64_t *seg_off, const double *t_rel, const double *a,
+                                    const double *trial, double *value, int32_t *status);
+int ionode_multi_exp_eval(int32_t n_seg, int32_t n_params, const double *x, const int64_t *full_off, const double *t_full, double *a_fit,
+                          double *dadt, double *d2adt2, void *stream);
+int ionode_multi_exp_eval_host(int32_t n_seg, int32_t n_params, const double *x, const int64_t *full_off, const double *t_full, double *a_fit,
+                               double *dadt, double *d2adt2);
+
 #ifdef __cplusplus
 }
 #endif

@@ -303,6 +303,12 @@ PROTOTYPES = {
     # d, active, sse, jtr, jtj, status, state, flag, iters, trial, samples (, stream)
     "ionode_mala_step": (C.c_int, [C.POINTER(IonodeMalaDesc)] + [_P] * 11),
     "ionode_mala_step_host": (C.c_int, [C.POINTER(IonodeMalaDesc)] + [_P] * 10),
+    # n_run, n_active, lambda, n_params, active, seg_of_run, seg_off, t_rel, a, trial, value, status (, stream)
+    "ionode_multi_exp_objective": (C.c_int, [_I32] * 4 + [_P] * 9),
+    "ionode_multi_exp_objective_host": (C.c_int, [_I32] * 4 + [_P] * 8),
+    # n_seg, n_params, x, full_off, t_full, a_fit, dadt, d2adt2 (, stream)
+    "ionode_multi_exp_eval": (C.c_int, [_I32] * 2 + [_P] * 7),
+    "ionode_multi_exp_eval_host": (C.c_int, [_I32] * 2 + [_P] * 6),
     "ionode_grad_reduce": (C.c_int, _REDUCE),
     "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
     "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),

@@ -78,8 +78,10 @@ def multi_exp(t, x, order=0):
 
 def fit_multi_exp(t, a, x0, restarts=0, seed=0):
     """Nelder-Mead minimisation of the RMSE of multi_exp(t, x) against a (scipy.optimize.fmin, as train-r1.py:487-489).  The
-    reference hands its hardest segments (the -90 mV steps) to PINTS' CMA-ES (train-r1.py:553-555); PINTS is an absent third-party
-    dependency, so `restarts` > 0 re-runs the simplex from log-normal perturbations of x0 (seeded) and keeps the best."""
+    reference hands its hardest segments (the -90 mV steps) to PINTS' CMA-ES (train-r1.py:553-555): that route is
+    expfit.fit_segments (every segment and restart of a protocol as CMA-ES runs advancing together on the GPU), which
+    fit_activation(fitter="cmaes") takes.  Here, on the host, `restarts` > 0 re-runs the simplex from log-normal perturbations of x0
+    (seeded) and keeps the best."""
     from scipy import optimize
     t, a = np.asarray(t, dtype=np.float64), np.asarray(a, dtype=np.float64)
     f = lambda x: np.sqrt(np.mean((multi_exp(t, x) - a) ** 2))
@@ -93,7 +95,7 @@ def fit_multi_exp(t, a, x0, restarts=0, seed=0):
 
 
 def fit_activation(prot_t, a, change_mask, cap_mask, std_cutoff=0.01, x0=TRI_EXP_X0, bi_exp_at=(), spline_at=(), restart_segments=(),
-                   restarts=4, spline_window=51, spline_k=4, spline_s=0.2):
+                   restarts=4, spline_window=51, spline_k=4, spline_s=0.2, fitter=None):
     """a(t), da/dt, d2a/dt2 on the whole time grid of one real-data protocol, segment by segment (train-r1.py:453-679).
 
     prot_t [n] sample times; a [n] the activation estimate i / (g r (V - E)); change_mask [n] False exactly AT the voltage change
@@ -104,8 +106,15 @@ def fit_activation(prot_t, a, change_mask, cap_mask, std_cutoff=0.01, x0=TRI_EXP
         segments whose index is in `restart_segments` take the restarted simplex (the reference's CMA-ES cases);
       * otherwise, or where the segment contains one of `spline_at` (the sine-wave window at 3500 ms: smooth(a, 21), k = 5,
         train-r1.py:565-573): Hanning smoothing + UnivariateSpline(k = spline_k, s = spline_s), derivatives from the spline.
+    fitter: None -- the simplex above, segment after segment; "cmaes" -- the reference's CMA-ES for ALL exponential segments:
+    every tri-exponential segment of the protocol goes into one expfit.fit_segments call and every bi-exponential segment into
+    another (`restarts` then applies to all of them, restart_segments is not consulted), and the curves and derivatives come from
+    expfit.evaluate; a dict -- "cmaes" with these keyword arguments for expfit.fit_segments (seed, max_iter, device, ...; its
+    device also serves expfit.evaluate).  Spline segments are the same either way.
     Returns (a_fit, dadt, d2adt2, kinds): arrays [n] (zero outside every fitted segment, as the reference leaves them) and the
     list of (t_first, t_last, 'tri-exp' | 'bi-exp' | 'spline') per segment."""
+    if fitter is not None and fitter != "cmaes" and not isinstance(fitter, dict):
+        raise ValueError("fit_activation: fitter is None, 'cmaes' or a dict of expfit.fit_segments keyword arguments")
     from scipy.interpolate import UnivariateSpline
     prot_t, a = np.asarray(prot_t, dtype=np.float64), np.asarray(a, dtype=np.float64).reshape(-1)
     change_mask, cap_mask = np.asarray(change_mask, dtype=bool), np.asarray(cap_mask, dtype=bool)
@@ -114,6 +123,7 @@ def fit_activation(prot_t, a, change_mask, cap_mask, std_cutoff=0.01, x0=TRI_EXP
     tt, aa = prot_t[cap_mask], a[cap_mask]
     ao, d1, d2 = np.zeros(prot_t.shape), np.zeros(prot_t.shape), np.zeros(prot_t.shape)
     kinds = []
+    batched = {False: [], True: []}   # fitter="cmaes": the tri- / bi-exponential segments as (t0, samples, full-grid times, full-grid indices)
     t_lo = 0
     for seg, t_hi in enumerate(t_split):
         idx = np.where((tt >= t_lo) & (tt < t_hi))[0]
@@ -126,16 +136,27 @@ def fit_activation(prot_t, a, change_mask, cap_mask, std_cutoff=0.01, x0=TRI_EXP
         if np.std(aa[idx]) > std_cutoff and not sine:
             bi = any(within(tfit, x) for x in bi_exp_at)
             t0 = tfit - tfit[0]
-            x = fit_multi_exp(t0, aa[idx], BI_EXP_X0 if bi else x0, restarts=restarts if seg in restart_segments else 0)
             tf = prot_t[full] - tfit[0]
-            ao[full], d1[full], d2[full] = multi_exp(tf, x), multi_exp(tf, x, 1), multi_exp(tf, x, 2)
             kinds.append((tfit[0], tfit[-1], "bi-exp" if bi else "tri-exp"))
+            if fitter is not None:   # pass 1: collected, fitted together below
+                batched[bi].append((t0, aa[idx], tf, full))
+                continue
+            x = fit_multi_exp(t0, aa[idx], BI_EXP_X0 if bi else x0, restarts=restarts if seg in restart_segments else 0)
+            ao[full], d1[full], d2[full] = multi_exp(tf, x), multi_exp(tf, x, 1), multi_exp(tf, x, 2)
         else:
             w, k = (21, 5) if sine else (spline_window, spline_k)
             spl = UnivariateSpline(tfit, smooth(aa[idx], w)[w // 2:-(w // 2)], k=k)
             spl.set_smoothing_factor(spline_s)
             ao[full], d1[full], d2[full] = spl(prot_t[full]), spl(prot_t[full], 1), spl(prot_t[full], 2)
             kinds.append((tfit[0], tfit[-1], "spline"))
+    for bi, segs in batched.items():
+        if segs:
+            from . import expfit
+            kw = dict(fitter) if isinstance(fitter, dict) else {}
+            x = expfit.fit_segments([s[0] for s in segs], [s[1] for s in segs], BI_EXP_X0 if bi else x0, restarts=restarts, **kw)[0]   # pass 1
+            curves = expfit.evaluate(x, [s[2] for s in segs], device=kw.get("device"))                                              # pass 2
+            for g, s in enumerate(segs):
+                ao[s[3]], d1[s[3]], d2[s[3]] = curves[0][g], curves[1][g], curves[2][g]
     return ao, d1, d2, kinds
 
 
