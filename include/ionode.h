@@ -987,6 +987,117 @@ int ionode_multi_exp_eval(int32_t n_seg, int32_t n_params, const double *x, cons
 int ionode_multi_exp_eval_host(int32_t n_seg, int32_t n_params, const double *x, const int64_t *full_off, const double *t_full, double *a_fit,
                                double *dadt, double *d2adt2);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Affine-invariant ensemble step: E independent ensembles of W walkers (all four models; new symbols, ABI stays 10).
+ * The two samplers above run every chain alone.  Here a walker's proposal is built from the CURRENT POSITIONS of the other walkers
+ * of its ensemble: Goodman and Weare's stretch move ("Ensemble samplers with affine invariance", Comm. App. Math. Comp. Sci. 5,
+ * 2010) in its parallel form (Foreman-Mackey et al., "emcee", 2013), or its differential-evolution sibling (ter Braak, "A Markov
+ * chain Monte Carlo version of the genetic algorithm Differential Evolution", Stat. Comput. 16, 2006) in the same two-halves
+ * form.  Nothing is tuned, nothing adapts, and both moves are invariant under affine maps of the search space.
+ *
+ * Layout.  W is even, H = W / 2; half 0 is walkers 0 .. H - 1, half 1 walkers H .. W - 1.  A full iteration is two calls: half 0
+ * moves with its partners drawn from half 1 as it stands, then half 1 with partners from half 0 -- a half's partners do not move
+ * until it has been told, which is what makes moving a whole half at once a valid Metropolis-Hastings step.  A half-iteration of
+ * all ensembles is two launches on one stream with no host synchronisation between them: the forward solve with the fused sum of
+ * squares on the first E H P rows of the trial tensor, then the entry point below.
+ *
+ * Coordinates, target, prior, box, sigma and n_samples are ionode_mcmc_step's: u_j = log x_j (log_parameters) or x_j for the n_free
+ * free parameters and, with sample_sigma, u_sigma = log sigma as the last; n = n_free + sample_sigma <= IONODE_MCMC_MAX_DIM;
+ * lp = -N u_sigma - (S / 2) exp(-2 u_sigma), S = sum_p value over p = 0 .. P - 1 in that order (a non-zero status on any of the P
+ * rows, or a NaN, makes S = +inf and lp = -inf), N = n_samples; the prior is uniform over the finite box in the search space.
+ *
+ * Calls.  An ensemble's counter t = iters[e][0] counts its calls.
+ *   t = 0    value / status hold E W P rows, walker k of ensemble e at rows (e W + k) P ..: the starts' evaluation.  Every walker's
+ *            lp is set and row 0 of samples written; IONODE_ENSEMBLE_NONFINITE if any start of the ensemble is outside the box or
+ *            has a non-finite lp.  Otherwise the ASK for half 0, and t <- 1.
+ *   t >= 1   value / status hold E H P rows, walker k of the half in turn at rows (e H + k) P ..  First the TELL for half
+ *            (t - 1) % 2; then, behind a workgroup barrier, the ASK for half t % 2, and t <- t + 1.  The call with t = 2 max_iter
+ *            tells half 1, sets IONODE_ENSEMBLE_MAXITER, asks nothing and leaves t: 2 max_iter + 1 calls make max_iter iterations.
+ *   ask      walker k of half h, partners from half 1 - h at their current u, w1 and w2 the two uniforms below:
+ *            IONODE_ENSEMBLE_STRETCH: j = min(floor(w1 H), H - 1); s = (a - 1) w2 + 1, z = (s s) / a, so z in [1 / a, a] with
+ *              density proportional to 1 / sqrt(z); ut = u_j + z (u_k - u_j); lq = (n - 1) log z (the library's log).
+ *            IONODE_ENSEMBLE_DE: two distinct partners ia = min(floor(w1 H), H - 1), ib = (ia + 1 + min(floor(w2 (H - 1)), H - 2))
+ *              mod H; ut = (u_k + gamma (u_ia - u_ib)) + jitter xi, xi one standard normal deviate per coordinate; lq = 0.
+ *            A ut outside the box (or not a number) is not redrawn: the walker's OUTSIDE word is set and its trial rows get its
+ *            current x (that solve is wasted; its tell rejects without using the value).  Otherwise xt = exp(ut) clamped into
+ *            [lo, hi] (the library's deterministic exp) or xt = ut, and the walker's P trial rows, (e H + k) P .., are base[] with
+ *            the free columns replaced by xt.  Sigma never enters the rows.
+ *   tell     lp_t from S at ut.  alpha = 0 if OUTSIDE or lp_t is not finite; otherwise ratio = (lp_t + lq) - lp.  Accepted iff
+ *            alpha > 0 and log w3 < ratio: then (u, x, lp) <- (ut, xt, lp_t) and accepted[e][walker] goes up.
+ *   record   after the tell of half 1 of full iteration i = t / 2 (t even, >= 2): if i % thin == 0 and i / thin < sample_cap, row
+ *            i / thin of samples[e][walker] <- (x [n_free], sigma if sampled, lp) for all W walkers.  samples may be NULL.
+ *   frozen   an ensemble whose flag is not 0: a later call changes nothing of its state, flag, iters, accepted or samples and
+ *            writes the current x of half 0's walkers into its H slots of the trial rows (as does the call that flags it).
+ * There is no active list and no compaction: nothing stops early.  iters [E][2]: (t, full iterations told).
+ *
+ * Random numbers: the CMA-ES step's generator, unchanged -- Philox4x32-10, key (low, high word of seed), the same 53-bit uniforms,
+ * PPND16 and logarithm.  The counter is (ensemble_base + e, t, walker, pair + 65536 role), t the counter of the call that draws and
+ * walker = 0 .. W - 1: role 0, pair 0: w1 = uniform of words 0, 1 and w2 = of words 2, 3 (the ask of call t); role 1, pair 0: w3 =
+ * uniform of words 0, 1 (the tell of call t); role 2, pair p: xi of coordinates 2 p and 2 p + 1 (the DE ask of call t); role 3,
+ * t = 0: the driver's spread of the starts.  A draw is a pure function of its indices: an ensemble's results do not depend on the
+ * other ensembles of the call, and ensemble e under base b equals ensemble 0 under base b + e.
+ *
+ * state [E][W][IONODE_ENSEMBLE_STATE_U + 4 n] fp64, per walker: [IONODE_ENSEMBLE_STATE_LP] lp, [IONODE_ENSEMBLE_STATE_LQ] lq of
+ * the proposal in flight, [IONODE_ENSEMBLE_STATE_OUTSIDE] 1 if it left the box, else 0; then u, ut, x, xt [n each; with
+ * sample_sigma the last entry of x and xt is sigma].  flag [E], iters [E][2], accepted [E][W] int32.  To start, the caller writes
+ * u = ut = the starts in the search space, x = xt = the starts, the starts into all E W P trial rows, and zeroes the rest.
+ * trial [E W P][n_params] (calls t >= 1 touch its first E H P rows only); samples [E][W][sample_cap][n + 1].
+ *
+ * Execution model: one 256-lane workgroup per ensemble, the walkers of the half in turn strided over its lanes, n a compile-time
+ * constant (1 .. 13).  Tell, __syncthreads(), ask: the partners' u are read from the state where the tell left them.  The one
+ * cross-lane datum besides, "a start is bad" at t = 0, is one LDS word every finder stores 1 into.  No atomics, no scratch, every
+ * sum in one written order.  The host entry point runs the same per-ensemble routine on host pointers as a single lane, no HIP
+ * call: its results equal the kernel's bit for bit.
+ * IONODE_ENSEMBLE_MAX_WALKERS: a half in eight passes of the workgroup.  More partners than 2048 buy the moves nothing, and past it
+ * one workgroup serialises work that further ensembles would spread over the compute units: split a larger population into more
+ * ensembles.
+ * Refusals, all before anything is touched, text in the gradient path's error string: IONODE_ERR_ARG for a NULL descriptor or
+ * buffer (samples may be NULL), everything ionode_mcmc_step refuses about n_free, n_params, the free indices, the box, sigma,
+ * thin and the counts (n_ens, n_prot, max_iter < 1; max_iter above 2^30 - 1), W odd, W < 2 (n + 1) (a half must affinely span the
+ * search space, or the moves stay in a subspace for ever), H < 2 for the DE move, W above IONODE_ENSEMBLE_MAX_WALKERS, n_ens W
+ * n_prot beyond 2^31 - 1 rows, a <= 1 (or not finite), gamma or jitter not finite, jitter < 0, an unknown move, a negative
+ * sample_cap, n_samples not positive and finite.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define IONODE_ENSEMBLE_MAX_WALKERS 4096
+#define IONODE_ENSEMBLE_STATE_LP 0
+#define IONODE_ENSEMBLE_STATE_LQ 1
+#define IONODE_ENSEMBLE_STATE_OUTSIDE 2
+#define IONODE_ENSEMBLE_STATE_U 3
+#define IONODE_ENSEMBLE_RUNNING 0
+#define IONODE_ENSEMBLE_MAXITER 1
+#define IONODE_ENSEMBLE_NONFINITE 2
+#define IONODE_ENSEMBLE_STRETCH 0
+#define IONODE_ENSEMBLE_DE 1
+
+typedef struct ionode_ensemble_desc {
+  int32_t n_ens;           /* E: ensembles the arrays hold, all of them launched */
+  int32_t n_walkers;       /* W: walkers of an ensemble, even */
+  int32_t n_prot;          /* P: trajectories per walker */
+  int32_t n_params;        /* NPAR: 8 (HH 2-state, NN-f, NN-d rate parameters) or 12 (6-state) */
+  int32_t n_free;          /* nf */
+  int32_t log_parameters;
+  int32_t sample_sigma;    /* 1: log sigma is the last coordinate, within [sigma_lo, sigma_hi]; 0: sigma is fixed */
+  int32_t max_iter;        /* full iterations: every walker decides max_iter times */
+  int32_t thin;            /* every thin-th full iteration is recorded */
+  int32_t sample_cap;      /* rows of samples[e][walker] */
+  int32_t ensemble_base;   /* index of the arrays' first ensemble among all ensembles of the run (sharding): the generator sees ensemble_base + e */
+  int32_t move;            /* IONODE_ENSEMBLE_STRETCH or IONODE_ENSEMBLE_DE */
+  int64_t seed;
+  double n_samples;        /* N: residuals behind S, P times the samples of a trace */
+  double sigma, sigma_lo, sigma_hi;
+  double a;                /* stretch: z in [1 / a, a]; > 1 (Goodman and Weare's 2) */
+  double gamma;            /* DE: the difference's factor (ter Braak's 2.38 / sqrt(2 n)) */
+  double jitter;           /* DE: standard deviation of the added noise, >= 0 */
+  int32_t free_idx[IONODE_LM_MAX_FREE];
+  double base[IONODE_LM_MAX_FREE];
+  double lo[IONODE_LM_MAX_FREE], hi[IONODE_LM_MAX_FREE];   /* the box, in the parameters: finite (log_parameters: lo > 0) */
+} ionode_ensemble_desc;
+
+int ionode_ensemble_step(const ionode_ensemble_desc *d, const double *value, const int32_t *status, double *state, int32_t *flag,
+                         int32_t *iters, int32_t *accepted, double *trial, double *samples, void *stream);
+int ionode_ensemble_step_host(const ionode_ensemble_desc *d, const double *value, const int32_t *status, double *state, int32_t *flag,
+                              int32_t *iters, int32_t *accepted, double *trial, double *samples);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,46 @@ def mala_state_views(state, nf, sample_sigma):
     return v
 
 
+# the affine-invariant ensemble step (include/ionode.h ionode_ensemble_desc, IONODE_ENSEMBLE_*): descriptor, state layout, flags, moves
+ENSEMBLE_MAX_WALKERS = 4096
+ENSEMBLE_STATE_LP, ENSEMBLE_STATE_LQ, ENSEMBLE_STATE_OUTSIDE, ENSEMBLE_STATE_U = range(4)
+ENSEMBLE_RUNNING, ENSEMBLE_MAXITER, ENSEMBLE_NONFINITE = range(3)
+ENSEMBLE_STRETCH, ENSEMBLE_DE = 0, 1
+ENSEMBLE_MOVES = {"stretch": ENSEMBLE_STRETCH, "de": ENSEMBLE_DE}
+ENSEMBLE_FLAG_TEXT = {0: "running", 1: "iteration cap", 2: "a start outside the box, or its log-posterior not finite"}
+ENSEMBLE_ROLE_ASK, ENSEMBLE_ROLE_ACCEPT, ENSEMBLE_ROLE_JITTER, ENSEMBLE_ROLE_SPREAD = range(4)   # the generator's fourth counter word / 65536
+
+
+class IonodeEnsembleDesc(C.Structure):
+    _fields_ = [
+        ("n_ens", C.c_int32), ("n_walkers", C.c_int32), ("n_prot", C.c_int32), ("n_params", C.c_int32), ("n_free", C.c_int32),
+        ("log_parameters", C.c_int32), ("sample_sigma", C.c_int32), ("max_iter", C.c_int32), ("thin", C.c_int32),
+        ("sample_cap", C.c_int32), ("ensemble_base", C.c_int32), ("move", C.c_int32), ("seed", C.c_int64),
+        ("n_samples", C.c_double), ("sigma", C.c_double), ("sigma_lo", C.c_double), ("sigma_hi", C.c_double),
+        ("a", C.c_double), ("gamma", C.c_double), ("jitter", C.c_double),
+        ("free_idx", C.c_int32 * LM_MAX_FREE), ("base", C.c_double * LM_MAX_FREE),
+        ("lo", C.c_double * LM_MAX_FREE), ("hi", C.c_double * LM_MAX_FREE),
+    ]
+
+
+def ensemble_state_doubles(n):
+    """fp64 words of one walker's state: lp, lq, the outside word, then u, ut, x, xt [n]; n = the free parameters plus one if sigma
+    is sampled."""
+    return ENSEMBLE_STATE_U + 4 * n
+
+
+def ensemble_state_views(state, nf, sample_sigma):
+    """Named views of a state array [E, W, ensemble_state_doubles(n)] (numpy or torch), n = nf + (1 if sample_sigma else 0): lp, lq,
+    outside [E, W]; u, ut, x, xt [E, W, n]."""
+    n = nf + (1 if sample_sigma else 0)
+    v = {"lp": state[..., ENSEMBLE_STATE_LP], "lq": state[..., ENSEMBLE_STATE_LQ], "outside": state[..., ENSEMBLE_STATE_OUTSIDE]}
+    o = ENSEMBLE_STATE_U
+    for name in ("u", "ut", "x", "xt"):
+        v[name] = state[..., o:o + n]
+        o += n
+    return v
+
+
 # Every symbol of include/ionode.h: name -> (restype, argtypes); lib() applies the table, EXPORTS is its keys.
 _D, _P, _I32, _I64, _F32 = C.POINTER(IonodeDesc), C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _SOLVE = [_D] + [_P] * 12   # ionode_dopri5: d, mlp_packed .. stats, stream -- the solve family's common prefix
@@ -303,6 +343,9 @@ PROTOTYPES = {
     # d, active, sse, jtr, jtj, status, state, flag, iters, trial, samples (, stream)
     "ionode_mala_step": (C.c_int, [C.POINTER(IonodeMalaDesc)] + [_P] * 11),
     "ionode_mala_step_host": (C.c_int, [C.POINTER(IonodeMalaDesc)] + [_P] * 10),
+    # d, value, status, state, flag, iters, accepted, trial, samples (, stream)
+    "ionode_ensemble_step": (C.c_int, [C.POINTER(IonodeEnsembleDesc)] + [_P] * 9),
+    "ionode_ensemble_step_host": (C.c_int, [C.POINTER(IonodeEnsembleDesc)] + [_P] * 8),
     # n_run, n_active, lambda, n_params, active, seg_of_run, seg_off, t_rel, a, trial, value, status (, stream)
     "ionode_multi_exp_objective": (C.c_int, [_I32] * 4 + [_P] * 9),
     "ionode_multi_exp_objective_host": (C.c_int, [_I32] * 4 + [_P] * 8),

@@ -1,5 +1,5 @@
 // ionode_step_capi.hpp -- host only: what the entry points of the optimiser steps (ionode_lm_capi.hip, ionode_cmaes_capi.hip,
-// ionode_mcmc_capi.hip, ionode_mala_capi.hip) share.  The refusal that sets ionode_grad_last_error(), the checks and the box every step descriptor carries
+// ionode_mcmc_capi.hip, ionode_mala_capi.hip, ionode_ensemble_capi.hip) share.  The refusal that sets ionode_grad_last_error(), the checks and the box every step descriptor carries
 // (n_free, n_params, free_idx, lo, hi, base, log_parameters), the seed split and the launch's tail.
 #pragma once
 

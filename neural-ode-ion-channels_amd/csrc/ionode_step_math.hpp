@@ -1,4 +1,4 @@
-// ionode_step_math.hpp -- what the optimiser steps (ionode_lm.hpp, ionode_cmaes.hpp, ionode_mcmc.hpp, ionode_mala.hpp) share on both sides of the
+// ionode_step_math.hpp -- what the optimiser steps (ionode_lm.hpp, ionode_cmaes.hpp, ionode_mcmc.hpp, ionode_mala.hpp, ionode_ensemble.hpp) share on both sides of the
 // bit-for-bit contract: the fp64 predicates, lm_exp, cm_log and the Philox / AS241 generator.  Every function is compiled for the
 // kernel and for the host mirror from this one text; each has ONE written operation sequence (fma only inside lm_exp, no libm / ocml
 // call).  The trial-row writers and the packed Cholesky loops stay per step: shared copies moved the kernels' register figures

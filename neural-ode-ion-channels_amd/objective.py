@@ -533,3 +533,63 @@ def population_mala(starts, protocols_v, data_i, t_eval, *, base_params, free=(0
     w = R * (n + 1)
     return (out[:, :w].reshape(-1, R, n + 1).contiguous(), out[:, w].contiguous(), out[:, w + 1].to(torch.int32),
             out[:, w + 2:].to(torch.int32).contiguous())
+
+
+def population_ensemble(starts, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, bounds, sigma=None,
+                        sigma_bounds=None, move="stretch", a=2.0, gamma=None, jitter=1e-5, walkers=None, spread=1e-3, seed=0, max_iter=1000,
+                        thin=1, prot_t0=0.0, prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0,
+                        obs_open_state_only=False, max_total_steps=1_000_000, max_step="auto", rtol=1e-7, atol=1e-9, group=None, device=None,
+                        solver=None, cost=None, model=capi.MODEL_HH2, weights=None, mlp_layers=0, mlp_width=0, weights_key=None):
+    """Batched affine-invariant ensemble sampling (the sampler whose proposals come from the other walkers' current positions: nothing
+    to tune, nothing to learn, indifferent to the posterior's scales and tilt): starts [E, W, len(free)] (or [E, W, len(free) + 1],
+    the last column sigma's start, when sigma is sampled) are the walkers of E independent ensembles; or [E, len(free)] (+ 1) centres
+    -- typically population_fit's optimum -- with walkers=W and spread (ensemble.spread_starts).  All ensembles advance together
+    (ensemble.sample: per half-iteration one fused forward solve of E * W / 2 * P trajectories and one ionode_ensemble_step launch,
+    no host read in the loop).  move "stretch" (Goodman and Weare 2010) or "de" (ter Braak 2006).
+
+    Models, bounds, sigma / sigma_bounds, max_step "auto" and the NN models' weights: as population_mcmc.  max_iter counts full
+    iterations.  Returns (samples [E, W, R, n + 1], acceptance [E, W], flag [E] int32, iterations [E, 2] int32 = (calls, full
+    iterations)) on the device, as ensemble.sample does; mcmc.rhat on samples.reshape(E * W, R, n + 1) is R-hat over all walkers --
+    the walkers of one ensemble are not independent chains.
+    Sharding as population_mcmc, by ENSEMBLE (contiguous, or equal cost with `cost` [E]); an ensemble's random numbers depend on
+    (seed, its index among all E ensembles, walker, call, role) only, so there is no communication during the run and one all-gather
+    at its end; an ensemble's samples do not depend on the shard it ran in.  `solver` (tests only): a stand-in with batched.solve's
+    signature on CPU tensors; the step then runs as ionode_ensemble_step_host.
+    """
+    from . import ensemble
+    D, npar = capi.n_state(model), capi.n_params(model)
+    free = [int(f) for f in free]
+    nf = len(free)
+    n = nf + int(sigma is None)
+    cand = np.asarray(starts, dtype=np.float64)
+    if cand.ndim not in (2, 3):
+        raise capi.IonodeError(f"population_ensemble: starts [E, W, {nf}] or centres [E, {nf}] with walkers= expected, got {tuple(cand.shape)}")
+    E = cand.shape[0]
+    base = np.asarray(base_params, dtype=np.float64)
+    if base.shape != (npar,) or len(y0) != D:
+        raise capi.IonodeError(f"model {model}: base_params [{npar}] and y0 of {D} states expected")
+    if bounds is None:
+        raise capi.IonodeError("population_ensemble: bounds = (lo, hi) are required: the box is the prior")
+    if (sigma is None) == (sigma_bounds is None):
+        raise capi.IonodeError("population_ensemble: exactly one of sigma (fixed noise) and sigma_bounds (sampled noise) must be given")
+    rank, world, bounds_r = distributed.population_shards(E, cost, group, "ensembles")
+    lo, hi = bounds_r[rank]
+    dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
+    def corner():
+        rows = base[None].copy()
+        rows[:, free] = np.asarray(bounds[1], dtype=np.float64)
+        return rows
+    max_step = _auto_max_step(max_step, model, corner, protocols_v)
+    smp, rate, flag, iters = ensemble.sample(model, cand[lo:hi], protocols_v, data_i, t_eval, base_params=base, free=free,
+                                             log_parameters=log_parameters, bounds=bounds, sigma=sigma, sigma_bounds=sigma_bounds, move=move, a=a,
+                                             gamma=gamma, jitter=jitter, walkers=walkers, spread=spread, seed=seed, max_iter=max_iter, thin=thin,
+                                             weights=weights, mlp_layers=mlp_layers, mlp_width=mlp_width, weights_key=weights_key, prot_t0=prot_t0,
+                                             prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e,
+                                             obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=float(max_step),
+                                             rtol=rtol, atol=atol, device=dev, solver=solver, ensemble_offset=lo)
+    W, R = smp.shape[1], smp.shape[2]
+    w = W * R * (n + 1)
+    out = torch.cat([smp.reshape(hi - lo, w), rate, flag.double()[:, None], iters.double()], dim=1)   # [ensembles, W R (n + 1) + W + 3]
+    out = distributed.all_gather_shards(out, bounds_r, rank, group)
+    return (out[:, :w].reshape(-1, W, R, n + 1).contiguous(), out[:, w:w + W].contiguous(), out[:, w + W].to(torch.int32),
+            out[:, w + W + 1:].to(torch.int32).contiguous())

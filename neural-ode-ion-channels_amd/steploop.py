@@ -1,5 +1,5 @@
 """What the drivers of the four batched optimiser and sampler steps share: fit.py (Levenberg-Marquardt), cmaes.py (CMA-ES), mcmc.py
-(adaptive Metropolis) and mala.py (manifold MALA).  Each of them evaluates a trial tensor of items x rows_per_item trajectories, hands
+(adaptive Metropolis), mala.py (manifold MALA) and ensemble.py (the affine-invariant ensemble sampler, which never compacts).  Each of them evaluates a trial tensor of items x rows_per_item trajectories, hands
 the result to its step (ionode_<x>_step on the current stream, ionode_<x>_step_host on CPU tensors) and, every compact_every iterations, packs the items
 still running into the front launch slots.  The pieces of that are here; the loops stay with the drivers, which differ on purpose in
 what comes first (the solve or the step), in how often they run and in when they read the flags.
