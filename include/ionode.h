@@ -1098,6 +1098,79 @@ int ionode_ensemble_step(const ionode_ensemble_desc *d, const double *value, con
 int ionode_ensemble_step_host(const ionode_ensemble_desc *d, const double *value, const int32_t *status, double *state, int32_t *flag,
                               int32_t *iters, int32_t *accepted, double *trial, double *samples);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Training through the solve: the update that follows the backward sweep (NN-f / NN-d; new symbols, ABI stays 10).
+ * The reference trains its nets by regression on da/dt estimates and only WATCHES the prediction loss
+ * torch.mean(torch.abs(pred_yo - data)) (train-r1.py:930-945).  The fused objective and its sweep give that loss and dL/dW through
+ * the dopri5 solve; the three launches below turn the sweep's fp64 accumulator into one guarded, norm-clipped torch.optim.Adam
+ * step on weights that stay in device memory, and rebuild both weight images from them.  All three are asynchronous on the
+ * caller's stream, none reads anything back, and the decision whether the step happens is taken on the device.
+ * n = the floats of the flat state dict of (mlp_layers, mlp_width): 3 N + L (N N + N) + N + 1.
+ *
+ * ionode_train_grad_norm.  grad[i] = (float)acc[padmap[i]], i = 0 .. n - 1: acc is the padded fp64 partial gradient (layout:
+ * ionode_grad_partial_floats), padmap int32 [n] the flat-to-padded map (an entry that names no word of acc gives 0).
+ * norm_partials [ionode_train_norm_partials(n)] fp64 receives sums of grad[i]^2: workgroup g of 256 lanes owns the elements
+ * 4096 g .. 4096 g + 4095, lane l sums the squares (in fp64) of i = 4096 g + l, + 256, ... ascending, and the 256 lane sums are
+ * combined in ONE WRITTEN ORDER: inside each of the four wavefronts the xor-butterfly v_l <- v_l + v_(l xor s), s = 32, 16, 8, 4, 2,
+ * 1, then (w_0 + w_1) + (w_2 + w_3) through LDS.  The grid is a function of n alone.
+ *
+ * ionode_train_apply.  norm = sqrt(norm_partials[0] + norm_partials[1] + ...) in index order.  loss [1] fp64: the loss the
+ * gradient belongs to.  state_in / state_out: two blocks of IONODE_TRAIN_STATE_DOUBLES fp64; the call READS state_in and WRITES the
+ * whole of state_out (the caller alternates two blocks, so that no workgroup reads what another has written):
+ *   [IONODE_TRAIN_STATE_T] applied steps t, [.._BETA1_T] beta1^t, [.._BETA2_T] beta2^t, [.._SKIPPED] skipped calls, and of the
+ *   call that wrote the block: [.._LOSS] its loss, [.._NORM] its norm, [.._SCALE] its clip scale (0 when skipped), [.._APPLIED] 1 or 0.
+ *   A fresh block is {0, 1, 1, 0, 0, 0, 0, 0}.
+ * If norm or loss is not finite the call is SKIPPED: weights, exp_avg, exp_avg_sq, t and the products stay, SKIPPED goes up by
+ * one.  Otherwise t <- t + 1, the products are advanced by ONE multiplication each (there is no pow: beta^t is the product of t
+ * factors, in fp64, of the betas as given: the doubles torch.optim.Adam raises to the power t), scale = min(1, max_norm / (norm + 1e-6)) -- torch.nn.utils.clip_grad_norm_; max_norm <= 0: no clip, scale
+ * exactly 1 -- and with g = grad[i] * (float)scale, element-wise in fp32, ionode_adam_step's operations in its order:
+ *   m = m + (g - m) (1 - beta1);  v = v beta2 + (g g) (1 - beta2)        (beta2, 1 - beta1, 1 - beta2: formed in fp64, rounded to fp32 once)
+ *   w = w - (lr / bc1) (m / (sqrt(v) / bc2s + eps)),  bc1 = (float)(1 - beta1^t), bc2s = (float)sqrt(1 - beta2^t).
+ * grad itself is left unclipped.  lr arrives from the host: a schedule counts calls, Adam's t counts applied steps.
+ *
+ * ionode_train_refresh.  forward_image [ionode_mlp_packed_floats()] and grad_image [ionode_grad_image_floats()] of `weights`
+ * from their int32 maps, one launch; grad_map and grad_image may both be NULL (a width the gradient path does not serve).  A
+ * map entry s means: s > 0: weights[s - 1]; 0: padding, +0.0f; IONODE_TRAIN_MAP_NEG_ZERO: -0.0f (the fill of the 4-trajectory and
+ * one-trajectory sections); s <= IONODE_TRAIN_MAP_PLUS_ZERO: weights[IONODE_TRAIN_MAP_PLUS_ZERO - s] + 0.0f (the scalar
+ * section's hidden biases); an entry that names no weight gives +0.0f.  The grad map is ionode_image_refresh's.  The forward map
+ * needs no packer of its own: ionode_mlp_pack of the values 1 .. n gives the indices and, in the sign bit of its zeros, the -0.0f
+ * fill; ionode_mlp_pack of n times -0.0f gives +0.0f exactly where a weight passes through "+ 0.0f".  With such maps the images
+ * equal ionode_mlp_pack / ionode_grad_pack of the same weights bit for bit, the sign of zeros included.
+ *
+ * The _host entry points run the same functions on host pointers with no HIP call, lane after lane in the written order; their
+ * results equal the kernels' bit for bit.
+ * Refusals, all before anything is touched, text in the gradient path's error string: IONODE_ERR_ARG for a NULL buffer, (mlp_layers,
+ * mlp_width) that is no net or n not its state-dict size, no hidden layer (grad_norm), state_in == state_out, betas outside
+ * [0, 1), eps <= 0, lr or max_norm not finite; IONODE_ERR_UNSUPPORTED for a width no image exists for.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define IONODE_TRAIN_STATE_DOUBLES 8
+#define IONODE_TRAIN_STATE_T 0
+#define IONODE_TRAIN_STATE_BETA1_T 1
+#define IONODE_TRAIN_STATE_BETA2_T 2
+#define IONODE_TRAIN_STATE_SKIPPED 3
+#define IONODE_TRAIN_STATE_LOSS 4
+#define IONODE_TRAIN_STATE_NORM 5
+#define IONODE_TRAIN_STATE_SCALE 6
+#define IONODE_TRAIN_STATE_APPLIED 7
+#define IONODE_TRAIN_MAP_NEG_ZERO (-1)
+#define IONODE_TRAIN_MAP_PLUS_ZERO (-2)
+
+int32_t ionode_train_norm_partials(int32_t n);
+int ionode_train_grad_norm(int32_t n, int32_t mlp_layers, int32_t mlp_width, const double *acc, const int32_t *padmap, float *grad,
+                           double *norm_partials, void *stream);
+int ionode_train_grad_norm_host(int32_t n, int32_t mlp_layers, int32_t mlp_width, const double *acc, const int32_t *padmap, float *grad,
+                                double *norm_partials);
+int ionode_train_apply(int32_t n, int32_t mlp_layers, int32_t mlp_width, const float *grad, const double *norm_partials, const double *loss,
+                       const double *state_in, double *state_out, float *weights, float *exp_avg, float *exp_avg_sq, float lr, double beta1,
+                       double beta2, float eps, double max_norm, void *stream);
+int ionode_train_apply_host(int32_t n, int32_t mlp_layers, int32_t mlp_width, const float *grad, const double *norm_partials,
+                            const double *loss, const double *state_in, double *state_out, float *weights, float *exp_avg,
+                            float *exp_avg_sq, float lr, double beta1, double beta2, float eps, double max_norm);
+int ionode_train_refresh(int32_t n, int32_t mlp_layers, int32_t mlp_width, const int32_t *forward_map, const int32_t *grad_map,
+                         const float *weights, float *forward_image, float *grad_image, void *stream);
+int ionode_train_refresh_host(int32_t n, int32_t mlp_layers, int32_t mlp_width, const int32_t *forward_map, const int32_t *grad_map,
+                              const float *weights, float *forward_image, float *grad_image);
+
 #ifdef __cplusplus
 }
 #endif

@@ -352,6 +352,16 @@ PROTOTYPES = {
     # n_seg, n_params, x, full_off, t_full, a_fit, dadt, d2adt2 (, stream)
     "ionode_multi_exp_eval": (C.c_int, [_I32] * 2 + [_P] * 7),
     "ionode_multi_exp_eval_host": (C.c_int, [_I32] * 2 + [_P] * 6),
+    # n, mlp_layers, mlp_width, then: acc, padmap, grad, norm_partials (, stream)
+    "ionode_train_norm_partials": (_I32, [_I32]),
+    "ionode_train_grad_norm": (C.c_int, [_I32] * 3 + [_P] * 5),
+    "ionode_train_grad_norm_host": (C.c_int, [_I32] * 3 + [_P] * 4),
+    # ... grad, norm_partials, loss, state_in, state_out, weights, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, max_norm (, stream)
+    "ionode_train_apply": (C.c_int, [_I32] * 3 + [_P] * 8 + [_F32, C.c_double, C.c_double, _F32, C.c_double, _P]),
+    "ionode_train_apply_host": (C.c_int, [_I32] * 3 + [_P] * 8 + [_F32, C.c_double, C.c_double, _F32, C.c_double]),
+    # ... forward_map, grad_map, weights, forward_image, grad_image (, stream)
+    "ionode_train_refresh": (C.c_int, [_I32] * 3 + [_P] * 6),
+    "ionode_train_refresh_host": (C.c_int, [_I32] * 3 + [_P] * 5),
     "ionode_grad_reduce": (C.c_int, _REDUCE),
     "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
     "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),

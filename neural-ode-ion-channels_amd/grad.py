@@ -43,6 +43,7 @@ DEFAULT_CKPT_CAP = 4096
 DEFAULT_RECORD_BUDGET = 64 << 30   # of 288 GB HBM3E per GPU: two record buffers of half of it (24 GB: +1.5 % sweep time; 96 GB: -0.5 %)
 DEFAULT_CKPT_BUDGET = 96 << 30   # bytes of accepted-step checkpoints one forward may allocate (a third of the 288 GB of HBM3E)
 MAX_RECOMPUTE_ITERS = 65535 * 4  # phase A launches dim3(tiles, ceil(iterations / GRAD_RECOMPUTE_IB = 4)): HIP caps grid.y at 65535
+RESIDENT_IMAGES = "resident"      # what stands for the host weights when cfg["device_images"] = (forward image, grad image) hands both in
 
 
 def _bounded_budget(requested, default, dev, share):
@@ -87,13 +88,17 @@ def stable_step_cap(model, params, prot_v, v_oob=-80.0, safety=3.0):
 def _forward_with_checkpoints(ctx, weights_flat, params, y0, cfg, objective):
     """The forward of both autograd Functions: capi.dopri5 with the packed image of weights_flat (None: a closed-form model), cfg's
     keywords and accepted-step checkpoints; objective: the fused objective of kind cfg["objective"] (sse_ref, obs_*; no state trace) instead of the states.
+    cfg["device_images"] = (forward image, grad image),
+    two device tensors (optional): the images the launches read, instead of packing and uploading weights_flat (then None) -- _sweep reads the second.
     The [B, cap, record] checkpoint buffer is sized by ckpt_cap / ckpt_budget_bytes and regrown (the forward runs again) until the steps
     of every trajectory that SUCCEEDED fit.  Saves what _backward reads on ctx and returns capi.dopri5's result."""
     dev = y0.device
     B, D = y0.shape
     L, N = cfg["mlp_layers"], cfg["mlp_width"]
     w_np, packed = None, None
-    if weights_flat is not None:
+    if cfg.get("device_images") is not None:   # (train.ThroughSolve: both images already lie in device memory; nothing is packed or uploaded)
+        w_np, packed = RESIDENT_IMAGES, cfg["device_images"][0]
+    elif weights_flat is not None:
         w_np = weights_flat.detach().to(torch.float32).cpu().numpy()
         from . import batched  # packed forward image: shared cache with the plain solve
         packed = batched.packed_weights(w_np, L, N, dev, key=cfg.get("weights_key"))
@@ -288,7 +293,10 @@ def _sweep(cfg, desc, w_np, need_w, params, ckpt, n_acc, g, fused):
         gc_desc = capi.IonodeDesc.from_buffer_copy(desc)
         gc_desc.v_at_outputs = vtab.data_ptr()
     n_iter = int(n_acc.max().item()) + 1
-    image = grad_image(w_np, L, N, dev, key=cfg.get("weights_key")) if w_np is not None else None
+    if cfg.get("device_images") is not None:
+        image = cfg["device_images"][1]
+    else:
+        image = grad_image(w_np, L, N, dev, key=cfg.get("weights_key")) if w_np is not None else None
     D, npar = desc.n_state, capi.n_params(desc.model)
     state = torch.empty((B, 2 * D + npar), dtype=torch.float64, device=dev)
     g_params = torch.zeros((B, npar), dtype=torch.float64, device=dev)
