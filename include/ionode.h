@@ -1171,6 +1171,73 @@ int ionode_train_refresh(int32_t n, int32_t mlp_layers, int32_t mlp_width, const
 int ionode_train_refresh_host(int32_t n, int32_t mlp_layers, int32_t mlp_width, const int32_t *forward_map, const int32_t *grad_map,
                               const float *weights, float *forward_image, float *grad_image);
 
+/* ---------------------------------------------------------------------------------------------------------------------
+ * Posterior predictive bands: moments and exact quantiles of the current ACROSS parameter draws (new symbols, ABI stays 10).
+ * After a posterior run (the three samplers above) a user wants, per protocol p and output sample k, the mean, the spread and a
+ * credible band of i(t_k) over the S draws, and with sigma the prediction band that includes the observation noise.  The traces
+ * of all draws would be S P Nt doubles; here they go by in chunks and only [P][Nt] moments and, for quantiles, the column store
+ * cols [P][Nt][S_cap] stay.
+ *
+ * ionode_predictive_accumulate folds one chunk.  trace [n_draw P][Nt] fp64, candidate-major (row = c P + p, c the draw within
+ * the chunk; the layout of the population functions' trial tensors), status [n_draw P] int32, sigma [>= draw_base + n_draw] fp64
+ * indexed by draw_base + c, or NULL: d->sigma for every draw.  State, carried from chunk to chunk:
+ * mean, m2, min, max [P][Nt] fp64 (fresh: 0, 0, +inf, -inf), count [P] int64 (fresh: 0), cols or NULL (no quantiles wanted).
+ * Element (p, k) walks c = 0 .. n_draw - 1 in that order; a row with status != 0 is skipped (count[p] does not advance, its
+ * slot cols[p][k][draw_base + c] is +inf); otherwise, with x = trace[c P + p][k] -- plus sigma z under d->noise, z the AS241
+ * normal deviate of the first uniform of the Philox counter (draw_offset + draw_base + c, p, k, IONODE_PREDICTIVE_TAG) under d->seed --
+ *   n <- n + 1;  delta = x - mean;  mean <- mean + delta / n;  m2 <- m2 + delta (x - mean);  min, max by < and >
+ * and cols[p][k][draw_base + c] = x.  Every operation has one written order and the random numbers are a function of the
+ * draw's index among all draws, so the state after all chunks does not depend on how the draws were cut into chunks, bit for bit.  The
+ * sample variance is m2 / (count - 1).  count[p] is advanced by a second launch on the same stream.
+ *
+ * ionode_predictive_quantiles: quant [P][Q][Nt] from cols and count.  Every column is read as order-preserving 64-bit keys
+ * (negative doubles: all bits flipped, the others: the sign bit set -- a total order, -0 before +0, +inf behind every finite
+ * value), padded to a power of two with the key of all ones, and sorted; with m = count[p] (at most S_cap) the m smallest are
+ * the surviving draws' values, and for each q: h = q (m - 1), lo = floor(h), g = h - lo, x_lo + g (x_hi - x_lo) with x_hi the
+ * element min(lo + 1, m - 1).  m = 0: NaN.  A NaN among the surviving values has no place in that order and is not supported.
+ *
+ * ionode_predictive_plan: pure host code.  out[0] the quantile kernel's LDS bytes (8 * 2^L, 2^L >= max(s_cap, 2)), out[1] the
+ * column store's bytes 8 n_prot n_out s_cap, out[2] L.  Refuses what ionode_predictive_quantiles refuses about the shape, and a
+ * column store above budget_bytes (budget_bytes <= 0: no budget).
+ *
+ * Execution model: accumulate runs one 64-lane workgroup per (protocol, 64 consecutive samples), a lane per sample; the chunk's
+ * rows are read along k (coalesced) in tiles of 32 draws and stored to cols along s through a padded LDS tile.  quantiles runs
+ * one workgroup per column with the keys in LDS (128 KiB at the cap) and a bitonic network.  No atomics, no scratch.  The _host
+ * entry points run the same element routines on host pointers with no HIP call; their results equal the kernels' bit for bit.
+ * Refusals, all before anything is touched, text in the gradient path's error string: IONODE_ERR_ARG for a NULL descriptor or
+ * buffer (sigma and cols may be NULL), n_prot (above 65 535 too), n_out or n_draw < 1, n_draw n_prot beyond 2^31 - 1 rows,
+ * draw_base or draw_offset < 0, noise with neither a sigma array nor a finite d->sigma >= 0, with cols: s_cap < 1 or draw_base + n_draw >
+ * s_cap; for the quantiles: n_q outside 1 .. IONODE_PREDICTIVE_MAX_Q, a q outside [0, 1] (or NaN), n_prot n_out beyond
+ * 2^31 - 1 columns; IONODE_ERR_UNSUPPORTED for s_cap above IONODE_PREDICTIVE_MAX_DRAWS (the message names max_draws, the
+ * argument of predictive.draws that thins a pool to fit) and for a column store above the budget.
+ * ------------------------------------------------------------------------------------------------------------------- */
+#define IONODE_PREDICTIVE_MAX_DRAWS 16384
+#define IONODE_PREDICTIVE_MAX_Q 16
+#define IONODE_PREDICTIVE_TAG 0x70720000u
+
+typedef struct ionode_predictive_desc {
+  int32_t n_prot;      /* P */
+  int32_t n_out;       /* Nt */
+  int32_t n_draw;      /* draws of this chunk: trace has n_draw * n_prot rows */
+  int32_t s_cap;       /* draws the column store holds per (p, k); ignored without cols */
+  int32_t draw_base;   /* index of the chunk's first draw among the caller's draws: its slot in cols and in the sigma array */
+  int32_t draw_offset; /* index of the caller's first draw among ALL draws of the run (sharding): the generator sees draw_offset + draw_base + c */
+  int32_t noise;       /* 1: accumulate and store i + sigma z */
+  int32_t reserved;    /* 0 */
+  int64_t seed;
+  double sigma;        /* the one noise level, used when the sigma array is NULL */
+} ionode_predictive_desc;
+
+int ionode_predictive_plan(int32_t n_prot, int32_t n_out, int32_t s_cap, int64_t budget_bytes, int64_t out[3]);
+int ionode_predictive_accumulate(const ionode_predictive_desc *d, const double *trace, const int32_t *status, const double *sigma,
+                                 double *mean, double *m2, double *min, double *max, int64_t *count, double *cols, void *stream);
+int ionode_predictive_accumulate_host(const ionode_predictive_desc *d, const double *trace, const int32_t *status, const double *sigma,
+                                      double *mean, double *m2, double *min, double *max, int64_t *count, double *cols);
+int ionode_predictive_quantiles(int32_t n_prot, int32_t n_out, int32_t s_cap, int32_t n_q, const double *q, const int64_t *count,
+                                const double *cols, double *quant, void *stream);
+int ionode_predictive_quantiles_host(int32_t n_prot, int32_t n_out, int32_t s_cap, int32_t n_q, const double *q, const int64_t *count,
+                                     const double *cols, double *quant);
+
 #ifdef __cplusplus
 }
 #endif

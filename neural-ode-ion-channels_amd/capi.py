@@ -294,6 +294,19 @@ def ensemble_state_views(state, nf, sample_sigma):
     return v
 
 
+# the posterior predictive bands (include/ionode.h ionode_predictive_desc, IONODE_PREDICTIVE_*)
+PREDICTIVE_MAX_DRAWS = 16384
+PREDICTIVE_MAX_Q = 16
+PREDICTIVE_TAG = 0x70720000
+
+
+class IonodePredictiveDesc(C.Structure):
+    _fields_ = [
+        ("n_prot", C.c_int32), ("n_out", C.c_int32), ("n_draw", C.c_int32), ("s_cap", C.c_int32), ("draw_base", C.c_int32),
+        ("draw_offset", C.c_int32), ("noise", C.c_int32), ("reserved", C.c_int32), ("seed", C.c_int64), ("sigma", C.c_double),
+    ]
+
+
 # Every symbol of include/ionode.h: name -> (restype, argtypes); lib() applies the table, EXPORTS is its keys.
 _D, _P, _I32, _I64, _F32 = C.POINTER(IonodeDesc), C.c_void_p, C.c_int32, C.c_int64, C.c_float
 _SOLVE = [_D] + [_P] * 12   # ionode_dopri5: d, mlp_packed .. stats, stream -- the solve family's common prefix
@@ -362,6 +375,13 @@ PROTOTYPES = {
     # ... forward_map, grad_map, weights, forward_image, grad_image (, stream)
     "ionode_train_refresh": (C.c_int, [_I32] * 3 + [_P] * 6),
     "ionode_train_refresh_host": (C.c_int, [_I32] * 3 + [_P] * 5),
+    "ionode_predictive_plan": (C.c_int, [_I32] * 3 + [_I64, C.POINTER(_I64 * 3)]),
+    # d, trace, status, sigma, mean, m2, min, max, count, cols (, stream)
+    "ionode_predictive_accumulate": (C.c_int, [C.POINTER(IonodePredictiveDesc)] + [_P] * 10),
+    "ionode_predictive_accumulate_host": (C.c_int, [C.POINTER(IonodePredictiveDesc)] + [_P] * 9),
+    # n_prot, n_out, s_cap, n_q, then: q (host), count, cols, quant (, stream)
+    "ionode_predictive_quantiles": (C.c_int, [_I32] * 4 + [_P] * 5),
+    "ionode_predictive_quantiles_host": (C.c_int, [_I32] * 4 + [_P] * 4),
     "ionode_grad_reduce": (C.c_int, _REDUCE),
     "ionode_grad_reduce_unit": (C.c_int, _REDUCE),
     "ionode_grad_reduce_slabs": (_I32, [_I32, _I32, _I64]),
@@ -463,6 +483,16 @@ def regress_plan(mlp_layers, mlp_width):
     if lib().ionode_regress_plan(int(mlp_layers), int(mlp_width), C.byref(out)) != 0:
         raise IonodeError(lib().ionode_grad_last_error().decode())
     return {"generic": bool(out[0]), "wg_per_cu": out[1], "lds_bytes": out[2]}
+
+
+def predictive_plan(n_prot, n_out, s_cap, budget_bytes=0):
+    """Plan of the predictive bands' quantile pass, pure host code (ionode_predictive_plan): the LDS bytes of the kernel that sorts a
+    column of s_cap draws, the sort length's logarithm and the bytes of the column store [n_prot, n_out, s_cap].  Raises IonodeError
+    with the library's message for s_cap above PREDICTIVE_MAX_DRAWS and for a store above budget_bytes (0: no budget)."""
+    out = (C.c_int64 * 3)()
+    if lib().ionode_predictive_plan(int(n_prot), int(n_out), int(s_cap), int(budget_bytes), C.byref(out)) != 0:
+        raise IonodeError(lib().ionode_grad_last_error().decode())
+    return {"lds_bytes": int(out[0]), "cols_bytes": int(out[1]), "sort_log2": int(out[2])}
 
 
 def dense_defer_plan(desc, want_current):

@@ -179,16 +179,23 @@ def sample(model, x0, protocols_v, data_i, t_eval, *, base_params, free=(0, 1, 2
     return samples, rate, flag, iters
 
 
+def kept(samples, flag=None, burn=0.5):
+    """The part of sampler output [K, R, n + 1] (numpy or torch) that diagnostics and predictions use, numpy [m, r, n]: the chains
+    whose flag is MCMC_MAXITER (flag None: all), the rows after the first `burn` fraction, the log-posterior column left out.  One
+    selection for rhat and predictive.draws."""
+    s = samples.detach().cpu().numpy() if isinstance(samples, torch.Tensor) else np.asarray(samples)
+    if flag is not None:
+        f = flag.detach().cpu().numpy() if isinstance(flag, torch.Tensor) else np.asarray(flag)
+        s = s[f == capi.MCMC_MAXITER]
+    return s[:, int(np.floor(float(burn) * s.shape[1])):, :-1]
+
+
 def rhat(samples, flag=None, burn=0.5):
     """Gelman and Rubin's potential scale reduction per coordinate: samples [K, R, n + 1] as `sample` returns them (numpy or torch; the
     last column, the log-posterior, is left out), over the chains whose flag is MCMC_MAXITER (flag None: all), after dropping the
     first `burn` fraction of the rows.  With m chains of r rows, W the mean of the chains' variances and B / r the variance of their
     means: sqrt(((r - 1) / r W + B / r) / W).  numpy [n]; NaN with fewer than two chains or two rows."""
-    s = samples.detach().cpu().numpy() if isinstance(samples, torch.Tensor) else np.asarray(samples)
-    if flag is not None:
-        f = flag.detach().cpu().numpy() if isinstance(flag, torch.Tensor) else np.asarray(flag)
-        s = s[f == capi.MCMC_MAXITER]
-    s = s[:, int(np.floor(float(burn) * s.shape[1])):, :-1]
+    s = kept(samples, flag, burn)
     m, r = s.shape[0], s.shape[1]
     if m < 2 or r < 2:
         return np.full(s.shape[2], np.nan)

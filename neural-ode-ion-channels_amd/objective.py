@@ -593,3 +593,81 @@ def population_ensemble(starts, protocols_v, data_i, t_eval, *, base_params, fre
     out = distributed.all_gather_shards(out, bounds_r, rank, group)
     return (out[:, :w].reshape(-1, W, R, n + 1).contiguous(), out[:, w:w + W].contiguous(), out[:, w + W].to(torch.int32),
             out[:, w + W + 1:].to(torch.int32).contiguous())
+
+
+def population_predictive(draws, protocols_v, t_eval, *, base_params, free=(0, 1, 2, 3), log_parameters=True, coordinates="parameters", sigma=None,
+                          quantiles=(0.025, 0.5, 0.975), noise=False, seed=0, chunk_bytes=1 << 30, budget_bytes=32 << 30, prot_t0=0.0,
+                          prot_dt=0.1, y0=(0.0, 1.0), state_dtype=torch.float32, obs_g=1.0, obs_e=-86.0, obs_open_state_only=False,
+                          max_total_steps=1_000_000, max_step="auto", rtol=1e-7, atol=1e-9, group=None, device=None, solver=None,
+                          model=capi.MODEL_HH2, weights=None, mlp_layers=0, mlp_width=0, weights_key=None):
+    """Posterior predictive bands of the current over parameter draws (predictive.draws of a sampler's output): per protocol and
+    output sample the mean, the standard deviation, the extremes and exact quantiles of i(t) -- of i(t) + sigma z with noise=True --
+    over draws [S, len(free)] (or [S, len(free) + 1], sigma last).  predictive.bands does the work: the draws are solved in chunks,
+    one fused forward solve with the current epilogue and one ionode_predictive_accumulate launch each, no host read between them,
+    and one ionode_predictive_quantiles launch at the end.  Returns predictive.Bands.
+
+    All four models; the NN models take one shared weight set and `free` indexes their 8 rate parameters.  max_step "auto" is
+    resolved ONCE, before sharding, to grad.stable_step_cap over all draws (non-finite rows left out), so that every rank integrates
+    the same function; the NN models carry no such cap and take 0.
+    Sharding: contiguous shards of equal count; a rank's noise is a function of a draw's index among ALL draws, so the values do not
+    depend on the shard.  The moments merge across the ranks by the pairwise Welford merge IN RANK ORDER -- n = n_a + n_b,
+    d = mean_b - mean_a, mean = mean_a + d n_b / n, m2 = m2_a + m2_b + d^2 n_a n_b / n -- after one all-gather: every rank returns
+    the same Bands, equal to the single-rank ones up to that merge's rounding (not bit for bit).  Exact quantiles need every draw of
+    a column on one device: with a group of more than one rank they are REFUSED (pass quantiles=None for the moments, or run the
+    quantiles on one rank); gathering the column stores is out of scope.
+    `solver` (tests only): a stand-in with batched.solve's signature on CPU tensors; the passes then run as the host mirrors."""
+    from . import predictive
+    npar = capi.n_params(model)
+    free = [int(f) for f in free]
+    base = np.asarray(base_params, dtype=np.float64)
+    if base.shape != (npar,):
+        raise capi.IonodeError(f"model {model}: base_params [{npar}] expected")
+    x, _ = predictive.parameters(draws, len(free), log_parameters=log_parameters, coordinates=coordinates)
+    d = np.asarray(draws.detach().cpu() if isinstance(draws, torch.Tensor) else draws, dtype=np.float64)
+    S = d.shape[0]
+    rank, world, bounds_r = distributed.population_shards(S, None, group, "draws")
+    q = tuple(quantiles) if quantiles is not None else ()
+    if world > 1 and q:
+        raise capi.IonodeError(f"population_predictive: exact quantiles need all draws of a column on one device and the group has {world} "
+                               "ranks: pass quantiles=None for the moments, or run the quantiles on one rank")
+    def rows():
+        r = np.tile(base, (S, 1))
+        r[:, free] = x
+        return r
+    max_step = _auto_max_step(max_step, model, rows, protocols_v)
+    lo, hi = bounds_r[rank]
+    dev = batched._dev(device) if solver is None else torch.device(device or "cpu")
+    P, Nt = np.asarray(protocols_v).shape[0], np.asarray(t_eval).shape[0]
+    if hi > lo:
+        b = predictive.bands(model, d[lo:hi], protocols_v, t_eval, base_params=base, free=free, log_parameters=log_parameters,
+                             coordinates=coordinates, sigma=sigma, quantiles=q, noise=noise, seed=seed, chunk_bytes=chunk_bytes,
+                             budget_bytes=budget_bytes, solver=solver, draw_offset=lo, weights=weights, mlp_layers=mlp_layers, mlp_width=mlp_width,
+                             weights_key=weights_key, prot_t0=prot_t0, prot_dt=prot_dt, y0=y0, state_dtype=state_dtype, obs_g=obs_g, obs_e=obs_e,
+                             obs_open_state_only=obs_open_state_only, max_total_steps=max_total_steps, max_step=float(max_step), rtol=rtol,
+                             atol=atol, device=dev)
+        if world == 1:
+            return b
+        st = {"mean": torch.nan_to_num(b.mean, nan=0.0), "m2": b.m2, "min": torch.nan_to_num(b.min, nan=float("inf")),
+              "max": torch.nan_to_num(b.max, nan=float("-inf")), "count": b.count}
+    else:
+        st = predictive.new_state(P, Nt, 1, dev, store=False)
+    import torch.distributed as dist
+    mine = torch.cat([torch.stack([st["mean"], st["m2"], st["min"], st["max"]]).reshape(4, P * Nt),
+                      st["count"].double()[None, :].expand(4, P)], dim=1).contiguous()   # [4, P Nt + P]: the counts ride along (exact in fp64)
+    parts = [torch.empty_like(mine) for _ in range(world)]
+    dist.all_gather(parts, mine, group=group)
+    acc = None
+    for part in parts:   # rank order
+        mom, n_b = part[:, :P * Nt].reshape(4, P, Nt), part[0, P * Nt:][:, None]
+        if acc is None:
+            acc, n_a = mom.clone(), n_b.clone()
+            continue
+        n = n_a + n_b
+        dlt = mom[0] - acc[0]
+        safe = n.clamp(min=1.0)
+        acc[0] = torch.where(n_b > 0, acc[0] + dlt * n_b / safe, acc[0])
+        acc[1] = torch.where(n_b > 0, acc[1] + mom[1] + dlt * dlt * n_a * n_b / safe, acc[1])
+        acc[2], acc[3] = torch.minimum(acc[2], mom[2]), torch.maximum(acc[3], mom[3])
+        n_a = n
+    merged = {"mean": acc[0], "m2": acc[1], "min": acc[2], "max": acc[3], "count": n_a[:, 0].to(torch.int64)}
+    return predictive.finish(merged, (), S)
